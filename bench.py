@@ -9,7 +9,16 @@ parameters are resident in HBM before the timed region.  With N > 1 GPUs every r
 own clip (weak scaling) and the flat fp32 gradient buffer is all-reduced (SUM, RCCL over xGMI)
 before every optimizer step — the data-parallel form of the reference's gradient accumulation.
 
-    python bench.py --gpus 1 --steps 200 --warmup 20
+A plain run sets up, warms up, times exactly --steps steps in one region and prints the result line
+(value = steps / wall time of that region, ms_per_step = its inverse in ms).  --full adds every other
+leg beside it: repeated timed regions (spread), the loop with the clip uploaded inside it, the
+per-step roofline / kernel breakdown, the 64-clip batched, nn.Module-surface and audio-extension legs,
+the CPU baseline, the untiled long clip beside --tile-bars and the tiled leg beside data parallelism.
+--dump-outputs DIR writes what the last timed step left to its caller (losses, parameters, Adam
+state, gradient buffers) as float32 .npy files; inputs are seeded, so runs with the same arguments
+can be compared output for output.
+
+    python bench.py --gpus 1 --steps 200 --warmup 20 [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -78,6 +87,20 @@ def init_params(native, dims, seed=108):
         fan = int(np.prod(shape[1:])) if len(shape) > 1 else shape[0]
         flat[off:off + n] = (torch.rand(n, generator=g) * 2 - 1) / fan ** 0.5
     return flat, table
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one float32 .npy per array (device tensors are synchronised and copied back)."""
+    host = {k: t.detach().float().cpu().numpy() for k, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f'--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit')
+    os.makedirs(path, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(path, k + '.npy'), a)
 
 
 def cpu_baseline(flat, table, clip, seconds):
@@ -442,7 +465,8 @@ def tiled_leg(native, nat, dev, flat, dist, rank, world, iters, warm):
     """BASELINE.json configs[4]: ONE long clip (C=8, R=151, T=4) whose bars are tiled over the ranks: every
     rank computes the per-position work of its contiguous bar tile, the bar-level chains run replicated, and the iteration
     is a sequence of phases with small all-reduces (SUM) in between (mst_tiled_phase), then the flat-gradient all-reduce and
-    Adam.  A step = one training iteration of the whole clip (strong scaling: the clip is fixed, the tiles shrink)."""
+    Adam.  A step = one training iteration of the whole clip (strong scaling: the clip is fixed, the tiles shrink).
+    Returns the result and the tensors the last step left (for --dump-outputs)."""
     from tools.synth import synth_clip
     C_, R_, T_ = LONG_CLIP['C'], LONG_CLIP['R'], LONG_CLIP['T']
     base, extra = divmod(R_, world)
@@ -495,7 +519,8 @@ def tiled_leg(native, nat, dev, flat, dist, rank, world, iters, warm):
                                      f'(BASELINE.json configs[4]): fwd+loss+bwd+Adam every step, {n_x[0] // max(iters, 1)} in-iteration '
                                      'all-reduces (SUM) of small workspace ranges + the flat-gradient all-reduce',
                             bars_per_rank=rows, hip_graph=False, collectives_per_iteration=n_x[0] // max(iters, 1) + (1 if dist is not None else 0),
-                            final_total_loss=float(losses.cpu()[0])))
+                            final_total_loss=float(losses.cpu()[0]))), \
+        dict(losses=losses, params=params, exp_avg=m, exp_avg_sq=v, adam_state=state, grads=g)
 
 
 def main():
@@ -506,23 +531,23 @@ def main():
     ap.add_argument('--no-graph', action='store_true', help='launch eagerly instead of replaying a hipGraph')
     ap.add_argument('--cpu-seconds', type=float, default=12.0)
     ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--breakdown', action='store_true', help='print the per-kernel time table to stderr')
+    ap.add_argument('--breakdown', action='store_true', help='with --full: print the per-kernel time table to stderr')
     ap.add_argument('--no-roofline', action='store_true',
-                    help='skip the per-step timing leg (PMC runs: its 2 x 21 extra launches of every step would count as traffic)')
+                    help='with --full: skip the per-step timing leg (PMC runs: its 2 x 21 extra launches of every step would count as traffic)')
     ap.add_argument('--backend', default='nccl', help='torch.distributed backend (nccl = RCCL); gloo only to rehearse N>1 on one GPU')
     ap.add_argument('--share-device', action='store_true', help='rehearsal: every rank uses cuda:0')
     ap.add_argument('--clips-per-gpu', type=int, default=1,
                     help='B > 1: B different clips per GPU in one batched plan (BASELINE.json configs[2]/[3]); a step is then one '
                          'clip-iteration, the optimizer steps once per pass over the B clips (iter_size = B per GPU)')
     ap.add_argument('--batched-clips', type=int, default=64,
-                    help='with the default one-clip workload on 1 GPU: also time this many clips in one batched plan (configs[2]) for '
+                    help='with --full and the default one-clip workload on 1 GPU: also time this many clips in one batched plan (configs[2]) for '
                          'a few passes and report it as "batched" in the same JSON line; 0 = skip')
     ap.add_argument('--batched-passes', type=int, default=12)
     ap.add_argument('--surface-steps', type=int, default=200,
-                    help='with the default workload on 1 GPU: also time this many loop bodies through the nn.Module surface '
+                    help='with --full and the default workload on 1 GPU: also time this many loop bodies through the nn.Module surface '
                          '(the drop-in path behind train-model.py) and report them as "surface"; 0 = skip')
     ap.add_argument('--audio-steps', type=int, default=200,
-                    help='with the default workload on 1 GPU: also time this many iterations of the AUDIO EXTENSION (no reference '
+                    help='with --full and the default workload on 1 GPU: also time this many iterations of the AUDIO EXTENSION (no reference '
                          'counterpart; reported as "audio_extension", never part of the headline); 0 = skip')
     ap.add_argument('--tile-bars', action='store_true',
                     help='headline = BASELINE.json configs[4] instead: ONE long clip (C=8, R=151, T=4) with its bars tiled over the '
@@ -532,6 +557,13 @@ def main():
                          'replayed on its own stream + eager Adam (experiment, slower)')
     ap.add_argument('--accum', choices=['streams', 'batched'], default='streams',
                     help='B = 1: run the iter_size = 2 accumulation iterations on two streams (default) or as one 2-clip batched pass')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every leg beside the headline (spread over repeated regions, with_upload, roofline and kernel '
+                         'breakdown, batched / surface / audio legs, CPU baseline, untiled long clip, tiled leg beside N > 1); '
+                         'the --batched-*, --surface-steps, --audio-steps, --cpu-seconds and --no-* options shape those legs')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last step left to its caller (losses, parameters, Adam state, '
+                         'gradient buffers) as DIR/<name>.npy, float32; rank 0 only')
     args = ap.parse_args()
 
     rank = int(os.environ.get('RANK', 0))
@@ -562,11 +594,15 @@ def main():
     dims = nat.Dims(**CLIP, **WIDTHS, instr=51, n_instruments=41, has_unpitched=1, clips=K)
     flat, table = init_params(native, dims1)
     if args.tile_bars:
-        r = tiled_leg(native, nat, dev, flat, dist, rank, world, args.steps, args.warmup)
-        # the untiled clip on ONE GPU (every rank measures its own card; rank 0 reports): strong-scaling denominator
-        un = long_clip_untiled(native, nat, dev, flat, max(10, args.steps // 2), 3)
-        r['config']['untiled_one_gpu'] = un
-        r['config']['speedup_vs_untiled_one_gpu'] = r['value'] / un['value']
+        r, outputs = tiled_leg(native, nat, dev, flat, dist, rank, world, args.steps, args.warmup)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, outputs)
+        del outputs
+        if args.full:
+            # the untiled clip on ONE GPU (every rank measures its own card; rank 0 reports): strong-scaling denominator
+            un = long_clip_untiled(native, nat, dev, flat, max(10, args.steps // 2), 3)
+            r['config']['untiled_one_gpu'] = un
+            r['config']['speedup_vs_untiled_one_gpu'] = r['value'] / un['value']
         if rank == 0:
             print(json.dumps(dict(metric='style-transfer opt iters/sec', value=r['value'], unit='iters/s', n_gpus=world, steps=args.steps,
                                   warmup=args.warmup, ms_per_step=r['ms_per_step'], higher_is_better=True, scaling='strong',
@@ -715,25 +751,31 @@ def main():
                 dt_ = float(t.cpu()[0])
             return dt_, ev0.elapsed_time(ev1)
 
-        # The region is repeated (whole regions of args.steps steps, never partial ones) until at least 0.25 s of timed work
-        # and 3 regions have been seen: at the driver's --steps 20 a single region is ~9 ms, i.e. ten graph replays.  value is
-        # the MEDIAN region; spread keeps the fastest and the slowest.  (Every rank derives the same repeat count from the
-        # MAX-reduced time of the first region.)
+        # value comes from ONE region of exactly args.steps steps.  With --full the region is then repeated (whole regions,
+        # never partial ones) until at least 0.25 s of timed work and 3 regions have been seen (at --steps 20 a single region
+        # is ~9 ms, i.e. ten graph replays), and spread keeps the fastest, the median and the slowest.  (Every rank derives
+        # the same repeat count from the MAX-reduced time of the first region.)
         regions = [timed_region()]
-        want = max(3, min(50, int(np.ceil(0.25 / max(regions[0][0], 1e-6)))))
-        while len(regions) < want:
-            regions.append(timed_region())
-        order = sorted(range(len(regions)), key=lambda i: regions[i][0])
-        dt, dev_ms = regions[order[len(order) // 2]]
-        spread = dict(repeats=len(regions), min_ms_per_step=regions[order[0]][0] / args.steps * 1e3,
-                      max_ms_per_step=regions[order[-1]][0] / args.steps * 1e3, value='median region')
+        dt, dev_ms = regions[0]
         final_loss = float(losses.cpu()[0, 0])
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, dict(losses=torch.stack(loss_out), params=params, exp_avg=m, exp_avg_sq=v,
+                                                 adam_state=state, grads=torch.stack(grads)))
+        spread = None
+        if args.full:
+            want = max(3, min(50, int(np.ceil(0.25 / max(dt, 1e-6)))))
+            while len(regions) < want:
+                regions.append(timed_region())
+            times = sorted(r[0] for r in regions)
+            spread = dict(repeats=len(regions), min_ms_per_step=times[0] / args.steps * 1e3,
+                          median_ms_per_step=times[len(times) // 2] / args.steps * 1e3,
+                          max_ms_per_step=times[-1] / args.steps * 1e3, value='first region')
 
         # ---- the same loop with the clip uploaded inside it (the reference's prepare_input moves every song to the device,
         # train-model.py:102-103): pinned host copies of the note tensors go to the device on a copy stream, double-buffered so
         # that the upload of pair i + 1 overlaps the compute of pair i; one graph per input buffer
         with_upload = None
-        if rank == 0 and world == 1 and not batched and (graph_pair is not None or lane_graphs is not None):
+        if args.full and rank == 0 and world == 1 and not batched and (graph_pair is not None or lane_graphs is not None):
             hxp, hxu = xp.cpu().pin_memory(), xu.cpu().pin_memory()
             bufs = [(xp, xu), (torch.empty_like(xp), torch.empty_like(xu))]
             graphs = [graph_pair, torch.cuda.CUDAGraph()]             # (this leg replays one joint graph per input buffer)
@@ -783,7 +825,7 @@ def main():
 
         # ---- roofline leg: every launch step timed with HIP events on this stream (same workload)
         roof, table_rows = None, []
-        if rank == 0 and not args.no_roofline:
+        if args.full and rank == 0 and not args.no_roofline:
             roof, table_rows = roofline_leg(plan, nat, params, gparams, xp, xu, K, dt / args.steps, args.breakdown, iter_size=iter_size)
 
     ips = world * args.steps / dt
@@ -807,11 +849,11 @@ def main():
     if with_upload is not None:
         out['value_with_upload'] = with_upload['value']
         out['with_upload'] = with_upload
-    if world > 1 and B == 1 and not batched:
+    if args.full and world > 1 and B == 1 and not batched:
         # configs[4] beside the data-parallel headline: the long clip with its bars tiled over the same ranks (never lets the
         # headline line fail)
         try:
-            tl = tiled_leg(native, nat, dev, flat, dist, rank, world, 10, 2)
+            tl, _ = tiled_leg(native, nat, dev, flat, dist, rank, world, 10, 2)
         except Exception as e:                      # noqa: BLE001
             tl = dict(error=repr(e))
         if rank == 0:
@@ -819,17 +861,17 @@ def main():
     if rank == 0:
         out['roofline'] = roof
         out['kernel_breakdown'] = table_rows
-        if world == 1 and B == 1 and not batched and args.batched_clips > 1:
+        if args.full and world == 1 and B == 1 and not batched and args.batched_clips > 1:
             del plan, ws                     # the one-clip workspaces are no longer needed
             out['batched'] = batched_leg(native, nat, dev, flat, args.batched_clips, args.batched_passes, 3)
-        if world == 1 and B == 1 and not batched and args.surface_steps > 0:
+        if args.full and world == 1 and B == 1 and not batched and args.surface_steps > 0:
             out['surface'] = surface_leg(dev, clip, args.surface_steps, 20)
-        if world == 1 and B == 1 and not batched and args.audio_steps > 0:
+        if args.full and world == 1 and B == 1 and not batched and args.audio_steps > 0:
             try:
                 out['audio_extension'] = audio_leg(nat, dev, args.audio_steps, 10, 0 if args.no_cpu_baseline else 4.0)
             except Exception as e:                      # noqa: BLE001  (an extension must never take the headline line down)
                 out['audio_extension'] = dict(error=repr(e))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(flat, table, clip, args.cpu_seconds)
         print(json.dumps(out))
     if dist is not None:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # developer loop: rebuild the interpreter library, run the CPU parity suite, (optionally) ASan, rebuild for gfx950
 set -e
-cd /root/repo
+cd "$(dirname "$0")/.."
 tests/hipsim/build.sh 2>&1 | grep -E "error|built" | head -8
 timeout 1500 python -m pytest tests/test_sim_parity.py -x -q 2>&1 | tail -2
 if [ "$1" = "asan" ]; then

@@ -35,7 +35,7 @@ def is_setup(name):
 
 def per_iteration(fetch, write, clips):
     # passes = launches of loss_tail_kernel (one per pass, nothing else launches it), counted PER RUN: the two counter runs
-    # repeat their timed region until 0.25 s have passed and need not make the same number of passes
+    # need not make the same number of passes (bench.py --full repeats its timed region until 0.25 s have passed)
     it_f, it_w = float(clips) * fetch['loss_tail_kernel']['launches'], float(clips) * write['loss_tail_kernel']['launches']
     def total(tab, setup):
         return sum(v['launches'] * v['avg_kb_per_launch'] for k, v in tab.items() if is_setup(k) == setup) * 1024
