@@ -201,8 +201,43 @@ enum { K_GEMM, K_GATHER, K_SEGRED, K_LSTM_F, K_LSTM_B, K_COMB_F, K_COMB_B, K_ME_
        // tiled plans only (never merged): halves of a combine, strided copies, fold / spread around an exchange, the exchange
        K_COMB_F1, K_COMB_F2, K_COMB_B1, K_COMB_B2, K_COPY_F, K_COPY_B, K_FOLD, K_SPREAD, K_XCHG,
        K_GEMM_FOLD,        // weight-gradient GEMMs of a batched plan with the clips folded into K (one descriptor for all clips)
-       K_CONV_P, K_CONV_F, K_CONV_W,
-       K_LIN_F, K_LIN_A, K_LIN_W };     // ... and its large dense nn.Linear layers (lin.hip): forward, input gradient, weight gradient      // batched plans on the 64x64 tiling: the note-axis convolution on its own kernels (conv.hip), one descriptor for all clips
+       K_CONV_P, K_CONV_F, K_CONV_W,    // batched plans on the 64x64 tiling: the note-axis convolution on its own kernels (conv.hip)
+       K_LIN_F, K_LIN_A, K_LIN_W,       // ... and its large dense nn.Linear layers (lin.hip): forward, input gradient, weight gradient
+       K_COUNT };
+// Per step kind (the values above are ABI: bench.py and the tests name them): the descriptor family Step.first indexes; sched:
+// in a scheduled list it indexes the family's scheduled (per-clip relocated) descriptors, not the build-time ones; per_clip: the
+// scheduler replicates the step per clip (K_GEMM_FOLD: one descriptor for all clips); merge: same-level steps may share a launch.
+enum { F_GEMM, F_GATHER, F_SEGRED, F_LSTM, F_COMB, F_NOTES, F_ROWLIN, F_COPY, F_FOLD, F_XCHG, F_CONV, F_LIN };
+struct KindInfo { int kind, fam, sched, per_clip, merge; };
+static constexpr KindInfo KINDS[] = {
+    {K_GEMM, F_GEMM, 1, 1, 1},     {K_GATHER, F_GATHER, 1, 1, 1}, {K_SEGRED, F_SEGRED, 1, 1, 1}, {K_LSTM_F, F_LSTM, 1, 1, 1},
+    {K_LSTM_B, F_LSTM, 1, 1, 1},   {K_COMB_F, F_COMB, 1, 1, 1},   {K_COMB_B, F_COMB, 1, 1, 1},   {K_ME_F, F_NOTES, 1, 1, 0},
+    {K_ME_B, F_NOTES, 1, 1, 0},    {K_PSA_F, F_NOTES, 1, 1, 0},   {K_PSA_B, F_NOTES, 1, 1, 0},   {K_LSTM_T, F_LSTM, 1, 1, 1},
+    {K_ROW_F, F_ROWLIN, 1, 1, 0},  {K_ROW_B, F_ROWLIN, 1, 1, 0},  {K_ME_SQ, F_NOTES, 1, 1, 0},   {K_ME_RED, F_NOTES, 1, 1, 0},
+    {K_COMB_F1, F_COMB, 1, 1, 0},  {K_COMB_F2, F_COMB, 1, 1, 0},  {K_COMB_B1, F_COMB, 1, 1, 0},  {K_COMB_B2, F_COMB, 1, 1, 0},
+    {K_COPY_F, F_COPY, 0, 0, 0},   {K_COPY_B, F_COPY, 0, 0, 0},   {K_FOLD, F_FOLD, 0, 0, 0},     {K_SPREAD, F_FOLD, 0, 0, 0},
+    {K_XCHG, F_XCHG, 0, 0, 0},     {K_GEMM_FOLD, F_GEMM, 1, 0, 1}, {K_CONV_P, F_CONV, 0, 0, 0},  {K_CONV_F, F_CONV, 0, 0, 0},
+    {K_CONV_W, F_CONV, 0, 0, 0},   {K_LIN_F, F_LIN, 0, 0, 0},     {K_LIN_A, F_LIN, 0, 0, 0},     {K_LIN_W, F_LIN, 0, 0, 0}};
+static constexpr bool kinds_in_order(int i = 0) { return i == K_COUNT || (KINDS[i].kind == i && kinds_in_order(i + 1)); }
+static_assert(sizeof(KINDS) / sizeof(KINDS[0]) == K_COUNT && kinds_in_order(), "KINDS[k] describes step kind k, for every k");
+
+template <class D>
+static int up(const std::vector<D>& v, D** dev) {
+    *dev = nullptr;
+    if (v.empty()) return 0;
+    if (hipMalloc((void**)dev, v.size() * sizeof(D)) != hipSuccess) return MST_ERR_ALLOC;
+    if (hipMemcpy(*dev, v.data(), v.size() * sizeof(D), hipMemcpyHostToDevice) != hipSuccess) return MST_ERR_ALLOC;
+    return 0;
+}
+// One descriptor family: as built (one clip), as scheduled (replicated families: per clip, relocated, in launch order) and on
+// the device — the scheduled copies, or the built ones for a family the scheduler never replicates (its `sched` stays empty).
+template <class D> struct DescTable {
+    std::vector<D> host, sched;
+    D* dev = nullptr;
+    int upload() { return up(sched.empty() ? host : sched, &dev); }
+    void release() { hipFree(dev); dev = nullptr; }
+};
+
 struct Step { int kind, first, count, a, b, stage; int c = 0; int lvl = 0; int chain = -1; int signal = -1; int wait[3] = {-1, -1, -1}; };
 // c: GEMM steps — offset of the step's block -> member table; lvl: dependency level in its scheduled pass; chain / signal / wait: the stream the
 // launch goes to, the event slot recorded behind it and the slots its stream waits for in front of it (assign_streams; chain -1 = caller's stream)
@@ -213,25 +248,20 @@ static int stage_idx(int stage) { return stage == MST_STAGE_EXTRACT ? 0 : stage 
 
 struct mst_plan {
     mst_dims d; Sizes z; ParamTable pt;
-    std::vector<GemmDesc> gemms; std::vector<GatherDesc> gathers; std::vector<SegRedDesc> segreds; std::vector<LstmDesc> lstms;
-    std::vector<CombineDesc> combines; std::vector<NotesDesc> notes; std::vector<RowLinDesc> rowlins; std::vector<SlabEntry> slabs[3];
-    std::vector<ConvDesc> convs; std::vector<LinDesc> lins;
+    DescTable<GemmDesc> gemms; DescTable<GatherDesc> gathers; DescTable<SegRedDesc> segreds; DescTable<LstmDesc> lstms;
+    DescTable<CombineDesc> combines; DescTable<NotesDesc> notes; DescTable<RowLinDesc> rowlins;
+    DescTable<ConvDesc> convs; DescTable<LinDesc> lins; DescTable<CopyDesc> copies; DescTable<FoldDesc> folds;
+    std::vector<SlabEntry> slabs[3];
     std::vector<Op> ops;
     // scheduled launch lists (dependency-levelled, same-level steps merged) and their descriptor arrays
     std::vector<Step> sched[2];        // per-stage merging (stages may run separately)
     std::vector<Step> sched_all[2];    // stage-agnostic merging, used when all stages run together
     const std::vector<Step>& list(int mask, int backward) const { return mask == MST_STAGE_ALL ? sched_all[backward ? 1 : 0] : sched[backward ? 1 : 0]; }
-    std::vector<GemmDesc> s_gemms; std::vector<GatherDesc> s_gathers; std::vector<SegRedDesc> s_segreds; std::vector<LstmDesc> s_lstms;
-    std::vector<CombineDesc> s_combines; std::vector<NotesDesc> s_notes; std::vector<RowLinDesc> s_rowlins;
-    RowLinDesc* d_rowlins = nullptr;
     // member of every workgroup of a clip's block range, per scheduled GEMM launch (Step.c): one uniform load instead of a binary
     // search over the members' first blocks — log2(members) dependent scalar round trips at the head of every workgroup
     std::vector<int> s_gemm_owner; int* d_gemm_owner = nullptr;
     std::map<std::string, T> named;
     int64_t act_top = 0, tmp_top = 0;
-    int64_t stage_begin[3] = {0, 0, 0}, stage_end[3] = {0, 0, 0};
-    GemmDesc* d_gemms = nullptr; GatherDesc* d_gathers = nullptr; SegRedDesc* d_segreds = nullptr; LstmDesc* d_lstms = nullptr;
-    CombineDesc* d_combines = nullptr; NotesDesc* d_notes = nullptr;     // d_notes: the scheduled (per-clip) copies, s_notes
     SlabEntry* d_slabs[3] = {nullptr, nullptr, nullptr};
     std::vector<SlabBlock> slab_blocks[3]; SlabBlock* d_slab_blocks[3] = {nullptr, nullptr, nullptr};
     // all three stages' entries as ONE launch (a whole-model backward): valid when no parameter range is the target of two entries
@@ -251,8 +281,7 @@ struct mst_plan {
     int P() const { return d.C * Rl() * d.T; }          // positions / beats this plan computes (all of them when not tiled)
     int Q() const { return Rl() * d.T; }
     struct Xchg { int space; int64_t off; int32_t len; };
-    std::vector<CopyDesc> copies; std::vector<FoldDesc> folds; std::vector<Xchg> xchgs;
-    CopyDesc* d_copies = nullptr; FoldDesc* d_folds = nullptr;
+    std::vector<Xchg> xchgs;
     bool tags_in_zero = false;             // zero_all also clears the multi-workgroup LSTM's exchange tags
     std::vector<ZeroChunk> zero_fwd; ZeroChunk* d_zero_fwd = nullptr;      // activation ranges cleared before a tiled forward
     int64_t loss_sum_off = 0;                                               // [SP_TMP] 16 floats: the loss partial sums, folded
@@ -358,6 +387,14 @@ struct mst_plan {
         n.itp_oct_off += a; n.itp_deg_off += a; n.loss_saved_off += a; n.loss_gl_off += a;
         return n;
     }
+    // f(table) for a family the scheduler replicates (KINDS[k].sched)
+    template <class F> void with_sched_table(int fam, F&& f) {
+        switch (fam) {
+        case F_GEMM: f(gemms); break;       case F_GATHER: f(gathers); break;     case F_SEGRED: f(segreds); break;
+        case F_LSTM: f(lstms); break;       case F_COMB: f(combines); break;      case F_NOTES: f(notes); break;
+        case F_ROWLIN: f(rowlins); break;   default: err = MST_ERR_UNSUPPORTED;
+        }
+    }
 
     static int64_t align(int64_t n) { return (n + 63) / 64 * 64; }
     T newT(int rows, int cols, const char* name = nullptr) {
@@ -397,11 +434,55 @@ struct mst_plan {
         return s < 1 ? 1 : (s > 64 ? 64 : s);
     }
 
+    // GEMM operands: a dense matrix (element (i, j) at off + i * si + j * sj); dY o act'(Y) of the output Y at `off` (transposed: j
+    // runs along Y's rows)
+    static Operand dense(int space, int64_t off, int64_t si, int64_t sj, int kfast, int ones_at = -1) {
+        Operand o{}; o.kind = OPK_DENSE; o.space = space; o.off = off; o.si = si; o.sj = sj; o.ones_at = ones_at; o.kfast = kfast;
+        return o;
+    }
+    static Operand actgrad(int64_t off, int ld, int act, bool transposed) {
+        Operand o{}; o.kind = OPK_ACTGRAD; o.space = SP_GRAD; o.off = off; o.space2 = SP_WS; o.off2 = off;
+        o.ld = ld; o.act = act; o.transposed = transposed ? 1 : 0; o.kfast = transposed ? 0 : 1;
+        return o;
+    }
+    // slab entries that reduce `splits` slabs (M x wcols weights, then M biases) into the weight gradient at woff (dst_ld > 0: a
+    // column block of a dst_ld-wide matrix at `base`) and the bias gradient at boff (none when < 0); single: one slab set for all clips
+    void weight_slabs(int stage, int64_t woff, int64_t boff, int64_t slab, int64_t stride, int M, int wcols, int splits, bool single,
+                      int dst_ld = 0, int64_t base = 0) {
+        SlabEntry e{woff, slab, stride, M * wcols, splits}, eb{boff, slab + (int64_t)M * wcols, stride, M, splits};
+        if (dst_ld) { e.width = wcols; e.dst_ld = dst_ld; e.base = base; }
+        e.single = eb.single = single ? 1 : 0;
+        slabs[stage_idx(stage)].push_back(e);
+        if (boff >= 0) slabs[stage_idx(stage)].push_back(eb);
+    }
+    // weight-gradient tail: `w` (M, operands, out.pb / pc set) over `rows` rows of one clip -> M x wcols weights (+ a bias column
+    // when boff >= 0), a k-split GEMM into a fresh slab, folded when may_fold on a plan that folds (`members` like GEMMs share its
+    // launch), and its slab entries.  Pushes the GEMM, returns its launch step
+    Step wgrad(int stage, GemmDesc w, int rows, int wcols, int64_t woff, int64_t boff, bool may_fold = true, int members = 1,
+               int dst_ld = 0, int64_t base = 0) {
+        w.N = wcols + (boff >= 0 ? 1 : 0); w.K = rows; w.ksplit = splits_for(rows);
+        const bool fd = may_fold && folds_clips();
+        if (fd) fold(w, rows, members);
+        const int64_t stride = (int64_t)w.M * wcols + w.M;
+        const int64_t slab = tmp(stride * w.ksplit);
+        w.out.kind = w.out.pb ? OUT_PERMW_SLAB : OUT_SLAB; w.out.space = SP_TMP; w.out.off = slab; w.out.slab_stride = stride;
+        w.out.wcols = wcols; w.out.bias_space = -1;
+        const Step st{fd ? K_GEMM_FOLD : K_GEMM, (int)gemms.host.size(), 1, tiles(w.M, w.N), w.ksplit};
+        gemms.host.push_back(w);
+        weight_slabs(stage, woff, boff, slab, stride, w.M, wcols, w.ksplit, fd, dst_ld, base);
+        return st;
+    }
+    // segment reduce of `nred` rows per output: one chunk per 64 rows; several chunks leave partial sums in scratch for a second
+    // launch, whose workgroup count is returned (0: none)
+    int partials(SegRedDesc& r, int nred) {
+        r.nchunk = (nred + 63) / 64;
+        if (r.nchunk <= 1) return 0;
+        r.part_off = tmp((int64_t)r.nidx * r.nchunk * r.width);
+        return (r.nidx * r.width + 255) / 256;
+    }
+
     static SegIn seg(const T& t, int s0, int s1, int s2, int s3, bool grad = true) {
         return SegIn{SP_WS, t.off, t.ld, t.cols, {s0, s1, s2, s3}, grad};
-    }
-    static SegIn segx(int space, int ld, int width, int s0, int s1, int s2, int s3) {
-        return SegIn{space, 0, ld, width, {s0, s1, s2, s3}, false};
     }
 
     // cat_with_broadcast (style/utils/pytorch.py:54-65) of several sources, materialised once.
@@ -423,9 +504,9 @@ struct mst_plan {
             if (!sum) start += segs[i].width;
         }
         Op op; op.stage = stage;
-        op.fwd.push_back(Step{K_GATHER, (int)gathers.size(), 1, rows, 0});
-        gathers.push_back(g);
-        int first = (int)segreds.size(), cnt = 0, maxidx = 1, stage2 = 0;
+        op.fwd.push_back(Step{K_GATHER, (int)gathers.host.size(), 1, rows, 0});
+        gathers.host.push_back(g);
+        int first = (int)segreds.host.size(), cnt = 0, maxidx = 1, stage2 = 0;
         start = 0;
         for (auto& s : segs) {
             if (s.grad) {
@@ -443,14 +524,9 @@ struct mst_plan {
                 }
                 int nred = 1;
                 for (int q = 0; q < 4; ++q) if (r.kd[q] == 1) nred *= rs[q];
-                r.nchunk = (nred + 63) / 64;
-                if (r.nchunk > 1) {
-                    r.part_off = tmp((int64_t)r.nidx * r.nchunk * r.width);
-                    const int b2 = (r.nidx * r.width + 255) / 256;
-                    if (b2 > stage2) stage2 = b2;
-                }
+                stage2 = std::max(stage2, partials(r, nred));
                 if (r.nidx * r.nchunk > maxidx) maxidx = r.nidx * r.nchunk;
-                segreds.push_back(r); ++cnt;
+                segreds.host.push_back(r); ++cnt;
             }
             if (!sum) start += s.width;
         }
@@ -486,60 +562,40 @@ struct mst_plan {
             l.rows_per_split = per; l.splits = (int)((mtot + per - 1) / per);
             l.slab_stride = (int64_t)N * K + N;
             l.slab_off = tmp(l.slab_stride * l.splits);
-            const int li = (int)lins.size();
-            lins.push_back(l);
+            const int li = (int)lins.host.size();
+            lins.host.push_back(l);
             op.fwd.push_back(Step{K_LIN_F, li, 1, 0, 0});
             op.bwd.push_back(Step{K_LIN_W, li, 1, 0, 0});
             if (xgrad) op.bwd.push_back(Step{K_LIN_A, li, 1, 0, 0});
-            SlabEntry e1{woff, l.slab_off, l.slab_stride, N * K, l.splits}, e2{boff, l.slab_off + (int64_t)N * K, l.slab_stride, N, l.splits};
-            e1.single = e2.single = 1;
-            slabs[stage_idx(stage)].push_back(e1);
-            slabs[stage_idx(stage)].push_back(e2);
+            weight_slabs(stage, woff, boff, l.slab_off, l.slab_stride, N, K, l.splits, true);
             ops.push_back(op);
             return out;
         }
-        {
-            GemmDesc g{}; g.M = rows; g.N = N; g.K = K; g.ksplit = 1;
-            g.A.kind = OPK_DENSE; g.A.space = space; g.A.off = xoff; g.A.si = xld; g.A.sj = 1; g.A.ones_at = -1; g.A.kfast = 1;
-            if (pb) { g.B.kind = OPK_PERMW; g.B.space = SP_PAR; g.B.off = woff; g.B.ld = K; g.B.pb = pb; g.B.pc = pc; g.B.kfast = 1; }
-            else { g.B.kind = OPK_DENSE; g.B.space = SP_PAR; g.B.off = woff; g.B.si = 1; g.B.sj = K; g.B.ones_at = -1; g.B.kfast = 1; }
-            g.out.kind = OUT_STORE; g.out.space = SP_WS; g.out.ldc = out.ld; g.out.act = act; g.out.off = out.off;
-            g.out.bias_space = SP_PAR; g.out.bias_off = boff;
-            // one row per clip (the style / song-info heads): batched plans on the 64x64 tiling run the clips as the rows of ONE
-            // GEMM (GemmDesc.clip_rows) — like the folded weight gradients, one descriptor for all clips
-            // (a one-clip plan on this tiling marks them too: the flag also pins the summation order, gemm.hip)
-            g.clip_rows = (mfma_plan() && rows == 1 && !pb && space == SP_WS) ? 1 : 0;
-            op.fwd.push_back(Step{(g.clip_rows && folds_clips()) ? K_GEMM_FOLD : K_GEMM, (int)gemms.size(), 1, tiles(rows, N), 1});
-            gemms.push_back(g);
-        }
-        {   // dW | db  =  (dY o act')^T [X | 1]
-            GemmDesc w{}; w.M = N; w.N = K + 1; w.K = rows; w.ksplit = splits_for(rows);
-            w.A.kind = OPK_ACTGRAD; w.A.space = SP_GRAD; w.A.off = out.off; w.A.space2 = SP_WS; w.A.off2 = out.off;
-            w.A.ld = out.ld; w.A.act = act; w.A.transposed = 1; w.A.kfast = 0;
-            w.B.kind = OPK_DENSE; w.B.space = space; w.B.off = xoff; w.B.si = xld; w.B.sj = 1; w.B.ones_at = K; w.B.kfast = 0;
-            const bool fd = folds_clips();
-            if (fd) fold(w, rows);
-            const int64_t stride = (int64_t)N * K + N;
-            const int64_t slab = tmp(stride * w.ksplit);
-            w.out.kind = pb ? OUT_PERMW_SLAB : OUT_SLAB; w.out.space = SP_TMP; w.out.off = slab; w.out.slab_stride = stride;
-            w.out.wcols = K; w.out.pb = pb; w.out.pc = pc; w.out.bias_space = -1;
-            op.bwd.push_back(Step{fd ? K_GEMM_FOLD : K_GEMM, (int)gemms.size(), 1, tiles(N, K + 1), w.ksplit});
-            gemms.push_back(w);
-            SlabEntry e1{woff, slab, stride, N * K, w.ksplit}, e2{boff, slab + (int64_t)N * K, stride, N, w.ksplit};
-            e1.single = e2.single = fd ? 1 : 0;
-            slabs[stage_idx(stage)].push_back(e1);
-            slabs[stage_idx(stage)].push_back(e2);
-        }
+        GemmDesc g{}; g.M = rows; g.N = N; g.K = K; g.ksplit = 1;
+        g.A = dense(space, xoff, xld, 1, 1);
+        if (pb) { g.B.kind = OPK_PERMW; g.B.space = SP_PAR; g.B.off = woff; g.B.ld = K; g.B.pb = pb; g.B.pc = pc; g.B.kfast = 1; }
+        else g.B = dense(SP_PAR, woff, 1, K, 1);
+        g.out.kind = OUT_STORE; g.out.space = SP_WS; g.out.ldc = out.ld; g.out.act = act; g.out.off = out.off;
+        g.out.bias_space = SP_PAR; g.out.bias_off = boff;
+        // one row per clip (the style / song-info heads): batched plans on the 64x64 tiling run the clips as the rows of ONE
+        // GEMM (GemmDesc.clip_rows) — like the folded weight gradients, one descriptor for all clips
+        // (a one-clip plan on this tiling marks them too: the flag also pins the summation order, gemm.hip)
+        g.clip_rows = (mfma_plan() && rows == 1 && !pb && space == SP_WS) ? 1 : 0;
+        op.fwd.push_back(Step{(g.clip_rows && folds_clips()) ? K_GEMM_FOLD : K_GEMM, (int)gemms.host.size(), 1, tiles(rows, N), 1});
+        gemms.host.push_back(g);
+        // dW | db  =  (dY o act')^T [X | 1]
+        GemmDesc w{}; w.M = N; w.A = actgrad(out.off, out.ld, act, true); w.B = dense(space, xoff, xld, 1, 0, K);
+        w.out.pb = pb; w.out.pc = pc;
+        op.bwd.push_back(wgrad(stage, w, rows, K, woff, boff));
         if (xgrad) {
             if (pb || space != SP_WS) { err = MST_ERR_UNSUPPORTED; }
             GemmDesc a{}; a.M = rows; a.N = K; a.K = N; a.ksplit = 1;
-            a.A.kind = OPK_ACTGRAD; a.A.space = SP_GRAD; a.A.off = out.off; a.A.space2 = SP_WS; a.A.off2 = out.off;
-            a.A.ld = out.ld; a.A.act = act; a.A.transposed = 0; a.A.kfast = 1;
-            a.B.kind = OPK_DENSE; a.B.space = SP_PAR; a.B.off = woff; a.B.si = K; a.B.sj = 1; a.B.ones_at = -1; a.B.kfast = 0;
+            a.A = actgrad(out.off, out.ld, act, false);
+            a.B = dense(SP_PAR, woff, K, 1, 0);
             a.out.kind = OUT_ACCUM; a.out.space = SP_GRAD; a.out.off = xoff; a.out.ldc = xld; a.out.bias_space = -1; a.out.act = ACT_NONE;
             a.clip_rows = (mfma_plan() && rows == 1 && !pb && space == SP_WS) ? 1 : 0;
-            op.bwd.push_back(Step{(a.clip_rows && folds_clips()) ? K_GEMM_FOLD : K_GEMM, (int)gemms.size(), 1, tiles(rows, K), 1});
-            gemms.push_back(a);
+            op.bwd.push_back(Step{(a.clip_rows && folds_clips()) ? K_GEMM_FOLD : K_GEMM, (int)gemms.host.size(), 1, tiles(rows, K), 1});
+            gemms.host.push_back(a);
         }
         ops.push_back(op);
         return out;
@@ -568,15 +624,12 @@ struct mst_plan {
             c.rows_per_split = per; c.splits = (int)((rows + per - 1) / per);
             c.slab_stride = (int64_t)z.OC * K + z.OC;
             c.slab_off = tmp(c.slab_stride * c.splits);
-            const int ci = (int)convs.size();
-            convs.push_back(c);
+            const int ci = (int)convs.host.size();
+            convs.host.push_back(c);
             op.fwd.push_back(Step{K_CONV_P, ci, 1, 0, 0});
             op.fwd.push_back(Step{K_CONV_F, ci, 1, 0, 0});
             op.bwd.push_back(Step{K_CONV_W, ci, 1, 0, 0});
-            SlabEntry e1{woff, c.slab_off, c.slab_stride, z.OC * K, c.splits}, e2{boff, c.slab_off + (int64_t)z.OC * K, c.slab_stride, z.OC, c.splits};
-            e1.single = e2.single = 1;
-            slabs[stage_idx(stage)].push_back(e1);
-            slabs[stage_idx(stage)].push_back(e2);
+            weight_slabs(stage, woff, boff, c.slab_off, c.slab_stride, z.OC, K, c.splits, true);
             ops.push_back(op);
             return x1;
         }
@@ -585,24 +638,15 @@ struct mst_plan {
         g.B.kind = OPK_PERMW; g.B.space = SP_PAR; g.B.off = woff; g.B.ld = K; g.B.pb = CONV_K; g.B.pc = NPF; g.B.kfast = 1;
         g.out.kind = OUT_CONV; g.out.space = SP_WS; g.out.off = x1.off; g.out.ldc = z.OC * NOCT;
         g.out.bias_space = SP_PAR; g.out.bias_off = boff;
-        op.fwd.push_back(Step{K_GEMM, (int)gemms.size(), 1, tiles(g.M, g.N), 1});
-        gemms.push_back(g);
-        GemmDesc w{}; w.M = z.OC; w.N = K + 1; w.K = P_ * NOCT; w.ksplit = splits_for(w.K);
+        op.fwd.push_back(Step{K_GEMM, (int)gemms.host.size(), 1, tiles(g.M, g.N), 1});
+        gemms.host.push_back(g);
+        GemmDesc w{}; w.M = z.OC;
         w.A.kind = OPK_CONVGRAD; w.A.space = SP_GRAD; w.A.off = x1.off; w.A.space2 = SP_WS; w.A.off2 = x1.off;
         w.A.oc = z.OC; w.A.kfast = 1;
         w.B.kind = OPK_IM2COL; w.B.space = SP_EXT0; w.B.off = 0; w.B.ones_at = K; w.B.kfast = 0;
-        const bool fd = folds_clips() && P_ * NOCT >= 64;      // the conv body's folded loader wants >= one k-tile of rows per clip
-        if (fd) fold(w, P_ * NOCT);
-        const int64_t stride = (int64_t)z.OC * K + z.OC;
-        const int64_t slab = tmp(stride * w.ksplit);
-        w.out.kind = OUT_PERMW_SLAB; w.out.space = SP_TMP; w.out.off = slab; w.out.slab_stride = stride; w.out.wcols = K;
-        w.out.pb = CONV_K; w.out.pc = NPF; w.out.bias_space = -1;
-        op.bwd.push_back(Step{fd ? K_GEMM_FOLD : K_GEMM, (int)gemms.size(), 1, tiles(w.M, w.N), w.ksplit});
-        gemms.push_back(w);
-        SlabEntry e1{woff, slab, stride, z.OC * K, w.ksplit}, e2{boff, slab + (int64_t)z.OC * K, stride, z.OC, w.ksplit};
-        e1.single = e2.single = fd ? 1 : 0;
-        slabs[stage_idx(stage)].push_back(e1);
-        slabs[stage_idx(stage)].push_back(e2);
+        w.out.pb = CONV_K; w.out.pc = NPF;
+        // the conv body's folded loader wants >= one k-tile of rows per clip
+        op.bwd.push_back(wgrad(stage, w, P_ * NOCT, K, woff, boff, P_ * NOCT >= 64));
         ops.push_back(op);
         return x1;
     }
@@ -618,9 +662,8 @@ struct mst_plan {
                                  sp.pre + ".bias_ih_l0" + sfx, 4 * sp.H, ACT_NONE));
         }
         Op op; op.stage = stage;
-        const int first = (int)lstms.size();
+        const int first = (int)lstms.host.size(), first_hh = (int)gemms.host.size();
         int maxB = 1, maxH = 1, minH = 1 << 30, maxTiles = 1, maxSplit = 1;
-        std::vector<GemmDesc> hh;
         for (size_t i = 0; i < specs.size(); ++i) {
             const LstmSpec& sp = specs[i];
             const int H = sp.H;
@@ -640,34 +683,24 @@ struct mst_plan {
                 l.multi = opt.lstm_flavour == 2 ? 2 : 1;
             l.xch_off = l.multi ? tmp(2 * (2 * H + 2 * 4 * H)) : 0;
             l.status_off = status_off;
-            lstms.push_back(l);
+            lstms.host.push_back(l);
             if (sp.B > maxB) maxB = sp.B;
             if (H > maxH) maxH = H;
             if (H < minH) minH = H;
-            GemmDesc w{}; w.M = 4 * H; w.N = H + 1; w.K = (int)n; w.ksplit = splits_for((int)n);
-            w.A.kind = OPK_DENSE; w.A.space = SP_GRAD; w.A.off = zxs[i].off; w.A.si = 1; w.A.sj = 4 * H; w.A.ones_at = -1; w.A.kfast = 0;
-            w.B.kind = OPK_DENSE; w.B.space = SP_TMP; w.B.off = l.hprev_off; w.B.si = H; w.B.sj = 1; w.B.ones_at = H; w.B.kfast = 0;
-            const bool fd = folds_clips();
-            if (fd) fold(w, (int)n, (int)specs.size());
-            const int64_t stride = (int64_t)4 * H * H + 4 * H;
-            const int64_t slab = tmp(stride * w.ksplit);
-            w.out.kind = OUT_SLAB; w.out.space = SP_TMP; w.out.off = slab; w.out.slab_stride = stride; w.out.wcols = H;
-            w.out.bias_space = -1;
-            hh.push_back(w);
-            if (tiles(w.M, w.N) > maxTiles) maxTiles = tiles(w.M, w.N);
-            if (w.ksplit > maxSplit) maxSplit = w.ksplit;
-            SlabEntry e1{whh, slab, stride, 4 * H * H, w.ksplit}, e2{bhh, slab + (int64_t)4 * H * H, stride, 4 * H, w.ksplit};
-            e1.single = e2.single = fd ? 1 : 0;
-            slabs[stage_idx(stage)].push_back(e1);
-            slabs[stage_idx(stage)].push_back(e2);
+            // W_hh | b_hh: the directions' weight-gradient GEMMs share one launch (pushed behind the recurrences)
+            GemmDesc w{}; w.M = 4 * H;
+            w.A = dense(SP_GRAD, zxs[i].off, 1, 4 * H, 0);
+            w.B = dense(SP_TMP, l.hprev_off, H, 1, 0, H);
+            const Step ws = wgrad(stage, w, (int)n, H, whh, bhh, true, (int)specs.size());
+            maxTiles = std::max(maxTiles, ws.a);
+            maxSplit = std::max(maxSplit, ws.b);
         }
         if (maxH > 64 && minH <= 64) err = MST_ERR_UNSUPPORTED;       // one register/L2 flavour per launch
         const int cnt = (int)specs.size();
         if (maxH > 64) op.fwd.push_back(Step{K_LSTM_T, first, cnt, 0, maxH});
         op.fwd.push_back(Step{K_LSTM_F, first, cnt, maxB, maxH});
         op.bwd.push_back(Step{K_LSTM_B, first, cnt, maxB, maxH});
-        op.bwd.push_back(Step{folds_clips() ? K_GEMM_FOLD : K_GEMM, (int)gemms.size(), cnt, maxTiles, maxSplit});
-        for (auto& w : hh) gemms.push_back(w);
+        op.bwd.push_back(Step{folds_clips() ? K_GEMM_FOLD : K_GEMM, first_hh, cnt, maxTiles, maxSplit});
         ops.push_back(op);
     }
     void lstm(int stage, const T& x, int B, int S, int H, int reverse, const std::string& pre, const T& out, int coloff) {
@@ -686,9 +719,9 @@ struct mst_plan {
         r.nblk = want < cap ? want : cap;
         r.slab_stride = N * x.cols + N; r.slab_off = tmp((int64_t)r.slab_stride * r.nblk);
         Op op; op.stage = stage;
-        op.fwd.push_back(Step{K_ROW_F, (int)rowlins.size(), 1, 0, 0});
-        op.bwd.push_back(Step{K_ROW_B, (int)rowlins.size(), 1, 0, 0});
-        rowlins.push_back(r); ops.push_back(op);
+        op.fwd.push_back(Step{K_ROW_F, (int)rowlins.host.size(), 1, 0, 0});
+        op.bwd.push_back(Step{K_ROW_B, (int)rowlins.host.size(), 1, 0, 0});
+        rowlins.host.push_back(r); ops.push_back(op);
         slabs[stage_idx(stage)].push_back(SlabEntry{r.w_off, r.slab_off, r.slab_stride, r.slab_stride, r.nblk});
         return out;
     }
@@ -706,62 +739,43 @@ struct mst_plan {
         const int rows = x.rows, kb = x.cols;
         const int64_t woff = pt.off(wname) + k0;
         Op op; op.stage = stage;
-        {
-            GemmDesc g{}; g.M = rows; g.N = N; g.K = kb; g.ksplit = 1;
-            g.A.kind = OPK_DENSE; g.A.space = SP_WS; g.A.off = x.off; g.A.si = x.ld; g.A.sj = 1; g.A.ones_at = -1; g.A.kfast = 1;
-            g.B.kind = OPK_DENSE; g.B.space = SP_PAR; g.B.off = woff; g.B.si = 1; g.B.sj = Kfull; g.B.ones_at = -1; g.B.kfast = 1;
-            g.out.kind = OUT_STORE; g.out.space = SP_WS; g.out.ldc = out.ld; g.out.act = act; g.out.off = out.off + col0;
-            g.out.bias_space = -1;
-            if (!bname.empty()) { g.out.bias_space = SP_PAR; g.out.bias_off = pt.off(bname); }
-            else if (bias_act) { g.out.bias_space = SP_WS; g.out.bias_off = bias_act->off + col0; }
-            else if (row_bias) { g.out.bias_space = SP_WS; g.out.bias_off = row_bias->off; g.out.bias_div = bias_div; g.out.bias_ld = row_bias->ld; }
-            if (row_bias && (rows % bias_div || row_bias->rows != rows / bias_div || row_bias->cols != N)) err = MST_ERR_UNSUPPORTED;
-            op.fwd.push_back(Step{K_GEMM, (int)gemms.size(), 1, tiles(rows, N), 1});
-            gemms.push_back(g);
-        }
+        GemmDesc g{}; g.M = rows; g.N = N; g.K = kb; g.ksplit = 1;
+        g.A = dense(SP_WS, x.off, x.ld, 1, 1);
+        g.B = dense(SP_PAR, woff, 1, Kfull, 1);
+        g.out.kind = OUT_STORE; g.out.space = SP_WS; g.out.ldc = out.ld; g.out.act = act; g.out.off = out.off + col0;
+        g.out.bias_space = -1;
+        if (!bname.empty()) { g.out.bias_space = SP_PAR; g.out.bias_off = pt.off(bname); }
+        else if (bias_act) { g.out.bias_space = SP_WS; g.out.bias_off = bias_act->off + col0; }
+        else if (row_bias) { g.out.bias_space = SP_WS; g.out.bias_off = row_bias->off; g.out.bias_div = bias_div; g.out.bias_ld = row_bias->ld; }
+        if (row_bias && (rows % bias_div || row_bias->rows != rows / bias_div || row_bias->cols != N)) err = MST_ERR_UNSUPPORTED;
+        op.fwd.push_back(Step{K_GEMM, (int)gemms.host.size(), 1, tiles(rows, N), 1});
+        gemms.host.push_back(g);
+        // dW block | db  =  dY^T [X | 1]
         const bool pbias = !bname.empty();
-        {   // dW block | db  =  dY^T [X | 1]
-            GemmDesc w{}; w.M = N; w.N = kb + (pbias ? 1 : 0); w.K = rows; w.ksplit = splits_for(rows);
-            if (act != ACT_NONE) {
-                w.A.kind = OPK_ACTGRAD; w.A.space = SP_GRAD; w.A.off = out.off + col0; w.A.space2 = SP_WS; w.A.off2 = out.off + col0;
-                w.A.ld = out.ld; w.A.act = act; w.A.transposed = 1; w.A.kfast = 0;
-            } else { w.A.kind = OPK_DENSE; w.A.space = SP_GRAD; w.A.off = out.off + col0; w.A.si = 1; w.A.sj = out.ld; w.A.ones_at = -1; w.A.kfast = 0; }
-            w.B.kind = OPK_DENSE; w.B.space = SP_WS; w.B.off = x.off; w.B.si = x.ld; w.B.sj = 1; w.B.ones_at = pbias ? kb : -1; w.B.kfast = 0;
-            const bool fd = folds_clips();
-            if (fd) fold(w, rows);
-            const int64_t stride = (int64_t)N * kb + N;
-            const int64_t slab = tmp(stride * w.ksplit);
-            w.out.kind = OUT_SLAB; w.out.space = SP_TMP; w.out.off = slab; w.out.slab_stride = stride; w.out.wcols = kb; w.out.bias_space = -1;
-            op.bwd.push_back(Step{fd ? K_GEMM_FOLD : K_GEMM, (int)gemms.size(), 1, tiles(w.M, w.N), w.ksplit});
-            gemms.push_back(w);
-            SlabEntry e{woff, slab, stride, N * kb, w.ksplit}; e.width = kb; e.dst_ld = Kfull; e.single = fd ? 1 : 0; e.base = pt.off(wname);
-            slabs[stage_idx(stage)].push_back(e);
-            if (pbias) { SlabEntry eb{pt.off(bname), slab + (int64_t)N * kb, stride, N, w.ksplit}; eb.single = fd ? 1 : 0; slabs[stage_idx(stage)].push_back(eb); }
-        }
+        const int64_t dy = out.off + col0;
+        GemmDesc w{}; w.M = N;
+        w.A = act != ACT_NONE ? actgrad(dy, out.ld, act, true) : dense(SP_GRAD, dy, 1, out.ld, 0);
+        w.B = dense(SP_WS, x.off, x.ld, 1, 0, pbias ? kb : -1);
+        op.bwd.push_back(wgrad(stage, w, rows, kb, woff, pbias ? pt.off(bname) : -1, true, 1, Kfull, pt.off(wname)));
         if (xgrad) {
             GemmDesc a{}; a.M = rows; a.N = kb; a.K = N; a.ksplit = 1;
-            if (act != ACT_NONE) {
-                a.A.kind = OPK_ACTGRAD; a.A.space = SP_GRAD; a.A.off = out.off + col0; a.A.space2 = SP_WS; a.A.off2 = out.off + col0;
-                a.A.ld = out.ld; a.A.act = act; a.A.transposed = 0; a.A.kfast = 1;
-            } else { a.A.kind = OPK_DENSE; a.A.space = SP_GRAD; a.A.off = out.off + col0; a.A.si = out.ld; a.A.sj = 1; a.A.ones_at = -1; a.A.kfast = 1; }
-            a.B.kind = OPK_DENSE; a.B.space = SP_PAR; a.B.off = woff; a.B.si = Kfull; a.B.sj = 1; a.B.ones_at = -1; a.B.kfast = 0;
+            a.A = act != ACT_NONE ? actgrad(dy, out.ld, act, false) : dense(SP_GRAD, dy, out.ld, 1, 1);
+            a.B = dense(SP_PAR, woff, Kfull, 1, 0);
             a.out.kind = OUT_ACCUM; a.out.space = SP_GRAD; a.out.off = x.off; a.out.ldc = x.ld; a.out.bias_space = -1; a.out.act = ACT_NONE;
-            op.bwd.push_back(Step{K_GEMM, (int)gemms.size(), 1, tiles(rows, kb), 1});
-            gemms.push_back(a);
+            op.bwd.push_back(Step{K_GEMM, (int)gemms.host.size(), 1, tiles(rows, kb), 1});
+            gemms.host.push_back(a);
         }
-        if (bias_act) column_sum(op, out.off + col0, out.ld, rows, N, bias_act->off + col0);
+        if (bias_act) column_sum(op, dy, out.ld, rows, N, bias_act->off + col0);
         if (row_bias) {          // g_row_bias[j] += sum of (dY o act')[j * bias_div .. + bias_div)
             SegRedDesc r{}; r.src_off = out.off; r.src_ld = out.ld; r.start = col0; r.width = N;
             r.dst_off = row_bias->off; r.dst_ld = row_bias->ld; r.nidx = rows / bias_div;
             const int rs[4] = {rows / bias_div, bias_div, 1, 1};
             for (int q = 0; q < 4; ++q) { r.d[q] = rs[q]; r.s[q] = 0; r.kd[q] = 1; }
             r.s[0] = 1; r.kd[0] = rows / bias_div;
-            r.nchunk = (bias_div + 63) / 64;
-            int stage2 = 0;
-            if (r.nchunk > 1) { r.part_off = tmp((int64_t)r.nidx * r.nchunk * N); stage2 = (r.nidx * N + 255) / 256; }
+            const int stage2 = partials(r, bias_div);
             r.act = act; r.y_off = out.off;
-            op.bwd.push_back(Step{K_SEGRED, (int)segreds.size(), 1, r.nidx * r.nchunk, stage2});
-            segreds.push_back(r);
+            op.bwd.push_back(Step{K_SEGRED, (int)segreds.host.size(), 1, r.nidx * r.nchunk, stage2});
+            segreds.host.push_back(r);
         }
         ops.push_back(op);
     }
@@ -810,37 +824,9 @@ struct mst_plan {
         SegRedDesc r{}; r.src_off = src_off; r.src_ld = src_ld; r.start = 0; r.width = width; r.dst_off = dst_off; r.dst_ld = width; r.nidx = 1;
         const int rs[4] = {rows, 1, 1, 1};
         for (int q = 0; q < 4; ++q) { r.d[q] = rs[q]; r.s[q] = 0; r.kd[q] = 1; }
-        r.nchunk = (rows + 63) / 64;
-        int stage2 = 0;
-        if (r.nchunk > 1) { r.part_off = tmp((int64_t)r.nchunk * width); stage2 = (width + 255) / 256; }
-        op.bwd.push_back(Step{K_SEGRED, (int)segreds.size(), 1, r.nidx * r.nchunk, stage2});
-        segreds.push_back(r);
-    }
-
-    // backward of "z[c, q] = rt[q] + it[c]" (rows c-major, `width` columns): g_rt[q] += sum_c g_z[c, q], g_it[c] += sum_q g_z[c, q]
-    // (with_rt = false: only g_it — the backward note kernel sums over the channels itself and writes g_rt)
-    void bcast_add_bwd(int stage, const T& gz, int Cn, int Qn, const T& rt, const T& it, bool with_rt) {
-        Op op; op.stage = stage;
-        const int first = (int)segreds.size();
-        int maxidx = 1, stage2 = 0;
-        for (int which = with_rt ? 0 : 1; which < 2; ++which) {
-            SegRedDesc r{}; r.src_off = gz.off; r.src_ld = gz.ld; r.start = 0; r.width = gz.cols;
-            const T& dst = which ? it : rt;
-            r.dst_off = dst.off; r.dst_ld = dst.ld;
-            const int rs[4] = {Cn, Qn, 1, 1};
-            for (int q = 0; q < 4; ++q) { r.d[q] = rs[q]; r.s[q] = 0; r.kd[q] = 1; }
-            if (which) { r.s[0] = 1; r.kd[0] = Cn; r.nidx = Cn; r.nchunk = (Qn + 63) / 64; }      // keep c, reduce q
-            else { r.s[1] = 1; r.kd[1] = Qn; r.nidx = Qn; r.nchunk = (Cn + 63) / 64; }            // keep q, reduce c
-            if (r.nchunk > 1) {
-                r.part_off = tmp((int64_t)r.nidx * r.nchunk * r.width);
-                const int b2 = (r.nidx * r.width + 255) / 256;
-                if (b2 > stage2) stage2 = b2;
-            }
-            if (r.nidx * r.nchunk > maxidx) maxidx = r.nidx * r.nchunk;
-            segreds.push_back(r);
-        }
-        op.bwd.push_back(Step{K_SEGRED, first, (int)segreds.size() - first, maxidx, stage2});
-        ops.push_back(op);
+        const int stage2 = partials(r, rows);
+        op.bwd.push_back(Step{K_SEGRED, (int)segreds.host.size(), 1, r.nidx * r.nchunk, stage2});
+        segreds.host.push_back(r);
     }
 
     // tiled: the exchange of one workspace range over the ranks (all-reduce SUM, done by the host between two phases).
@@ -857,17 +843,17 @@ struct mst_plan {
     void copy_rows(Op& op, int64_t src_off, int src_sa, int src_sb, int64_t dst_off, int dst_sa, int dst_sb, int na, int nb, int cols) {
         CopyDesc c{}; c.src_off = src_off; c.dst_off = dst_off; c.na = na; c.nb = nb; c.cols = cols;
         c.src_sa = src_sa; c.src_sb = src_sb; c.dst_sa = dst_sa; c.dst_sb = dst_sb;
-        op.fwd.insert(op.fwd.begin(), Step{K_COPY_F, (int)copies.size(), 1, 0, 0});
-        op.bwd.push_back(Step{K_COPY_B, (int)copies.size(), 1, 0, 0});
-        copies.push_back(c);
+        op.fwd.insert(op.fwd.begin(), Step{K_COPY_F, (int)copies.host.size(), 1, 0, 0});
+        op.bwd.push_back(Step{K_COPY_B, (int)copies.host.size(), 1, 0, 0});
+        copies.host.push_back(c);
     }
     // tiled: rank-local partial sums -> `sum` (exchanged) -> back as the only non-zero partial
     void fold_exchange(std::vector<Step>& steps, size_t at, int space, int64_t part_off, int nrows, int row_stride, int ncols,
                        int col_stride) {
         FoldDesc f{}; f.space = space; f.part_off = part_off; f.nrows = nrows; f.row_stride = row_stride; f.ncols = ncols;
         f.col_stride = col_stride; f.sum_off = tmp(ncols);
-        const int fi = (int)folds.size();
-        folds.push_back(f);
+        const int fi = (int)folds.host.size();
+        folds.host.push_back(f);
         const int xi = (int)xchgs.size();
         xchgs.push_back(Xchg{SP_TMP, f.sum_off, ncols});
         std::vector<Step> ins = {Step{K_FOLD, fi, 1, 0, 0}, Step{K_XCHG, xi, 1, 0, 0}, Step{K_SPREAD, fi, 1, 0, 0}};
@@ -885,16 +871,16 @@ struct mst_plan {
         const int large = (int64_t)rows * cols > COMBINE_SMALL ? 1 : 0;     // Step.b: 1 = needs the two-launch path
         Op op; op.stage = stage;
         if (global && tiled()) {
-            const int ci = (int)combines.size();
+            const int ci = (int)combines.host.size();
             op.fwd = {Step{K_COMB_F1, ci, 1, c.nblk, 0}, Step{K_COMB_F2, ci, 1, c.nblk, 0}};
             fold_exchange(op.fwd, 1, SP_TMP, c.part_off, c.nblk, COMBINE_MAXC + 1, Cn, 1);
             op.bwd = {Step{K_COMB_B1, ci, 1, c.nblk, 0}, Step{K_COMB_B2, ci, 1, c.nblk, 0}};
             fold_exchange(op.bwd, 1, SP_TMP, c.part_off, c.nblk, COMBINE_MAXC + 1, Cn + 1, 1);
         } else {
-            op.fwd.push_back(Step{K_COMB_F, (int)combines.size(), 1, c.nblk, large});
-            op.bwd.push_back(Step{K_COMB_B, (int)combines.size(), 1, c.nblk, large});
+            op.fwd.push_back(Step{K_COMB_F, (int)combines.host.size(), 1, c.nblk, large});
+            op.bwd.push_back(Step{K_COMB_B, (int)combines.host.size(), 1, c.nblk, large});
         }
-        combines.push_back(c);
+        combines.host.push_back(c);
         ops.push_back(op);
     }
 
@@ -924,11 +910,8 @@ void mst_plan::build() {
     t_losses = newT(1, 64, "losses"); t_saved = newT(1, MST_LOSS_SAVED, "loss_saved"); t_gl = newT(1, 64, "grad_losses");
     loss_scratch = tmp(mst_loss_scratch_floats());
     auto seg0 = [&](const T& t) { return seg(t, 0, 0, 0, 0, true); };      // broadcast over every row
-    auto rowsT = [&](const T& t, int rows, int cols, int ld) { return T{t.off, rows, cols, ld}; };
-    (void)rowsT;
 
     // ================================================================= stage 1: extract_style
-    stage_begin[0] = act_top;
     std::string m = "pitched_channels_encoder";
     T pce_il = linear(E, instr, false, m + ".instruments_linear", z.PCE_IL, ACT_LEAKY);
     T x1 = conv(E);
@@ -1060,22 +1043,21 @@ void mst_plan::build() {
         const int want = (P_ + 1) / 2;
         n.nblk = want < me_blk ? want : me_blk; n.slab_stride = nw; n.slab_off = tmp((int64_t)nw * n.nblk);
         Op op; op.stage = E;
-        op.fwd.push_back(Step{K_ME_SQ, (int)notes.size(), 1, 0, 0});
-        op.fwd.push_back(Step{K_ME_F, (int)notes.size(), 1, 0, 0});
-        op.bwd.push_back(Step{K_ME_RED, (int)notes.size(), 1, 0, 0});
-        op.bwd.push_back(Step{K_ME_B, (int)notes.size(), 1, 0, 0});
+        const int ni = (int)notes.host.size();
+        op.fwd.push_back(Step{K_ME_SQ, ni, 1, 0, 0});
+        op.fwd.push_back(Step{K_ME_F, ni, 1, 0, 0});
+        op.bwd.push_back(Step{K_ME_RED, ni, 1, 0, 0});
+        op.bwd.push_back(Step{K_ME_B, ni, 1, 0, 0});
         if (TL) {      // the channel norms are over every rank's positions
             fold_exchange(op.fwd, 1, SP_TMP, n.part_off, n.nwc, 1, C, n.nwc);
             fold_exchange(op.bwd, 1, SP_TMP, n.part_off, n.nwc, 1, C + 1, n.nwc);
         }
-        notes.push_back(n); ops.push_back(op);
+        notes.host.push_back(n); ops.push_back(op);
         // channels_linear.{weight,bias}, linear.{weight,bias} are contiguous in the flat buffer
         slabs[0].push_back(SlabEntry{n.wc_off, n.slab_off, nw, nw, n.nblk});
     }
-    stage_end[0] = act_top;
 
     // ================================================================= stage 2: predict_song_info
-    stage_begin[1] = act_top;
     m = "song_info_model";
     T rhy_rows{rhythm.off, Q_, NF * z.RH, NF * z.RH};                    // squash_dims(rhythm, -2)
     T sbl = newT(Q_, z.SIM_BL);
@@ -1102,10 +1084,8 @@ void mst_plan::build() {
         T hcat = gather(IN, RS1, {seg0(hs), seg0(hr)});
         linear(IN, hcat, true, m + "." + h.nm + "_linear", h.n, h.act, h.out);
     }
-    stage_end[1] = act_top;
 
     // ================================================================= stage 3: apply_style
-    stage_begin[2] = act_top;
     m = "pitched_style_applier";
     T psa_sl = linear(AP, style, true, m + ".style_linear", z.PSA_SL, ACT_LEAKY);
     T psa_rl = linear(AP, rhythm, true, m + ".rhythm_linear", z.PSA_RL, ACT_LEAKY);
@@ -1158,9 +1138,9 @@ void mst_plan::build() {
         const int nw = z.PSA_ML * z.MEL + z.PSA_ML + NPF * (NPF * 6 + z.PSA_ML) + NPF;
         n.nblk = psa_nblk; n.slab_stride = nw; n.slab_off = tmp((int64_t)nw * n.nblk);
         Op op; op.stage = AP;
-        op.fwd.push_back(Step{K_PSA_F, (int)notes.size(), 1, 0, 0});
-        op.bwd.push_back(Step{K_PSA_B, (int)notes.size(), 1, 0, 0});
-        notes.push_back(n); ops.push_back(op);
+        op.fwd.push_back(Step{K_PSA_F, (int)notes.host.size(), 1, 0, 0});
+        op.bwd.push_back(Step{K_PSA_B, (int)notes.host.size(), 1, 0, 0});
+        notes.host.push_back(n); ops.push_back(op);
         slabs[2].push_back(SlabEntry{n.wm_off, n.slab_off, nw, nw, n.nblk});
     }
     if (U) {
@@ -1174,7 +1154,6 @@ void mst_plan::build() {
         T v_rows{v.off, Q_ * NF * NUN, NUF * 4, NUF * 4};                  // x.view(..., n_unpitched_notes, -1)
         rowlin(AP, v_rows, true, m + ".linear", NUF, ACT_SIGOUT, "unpitched_pred");
     }
-    stage_end[2] = act_top;
     if (!notes_widths_supported(z.MEL, z.ME_CW, z.PSA_ML)) err = MST_ERR_UNSUPPORTED;
     if (z.H > 256 || z.SE_L > 256 || z.HB > 256) err = MST_ERR_UNSUPPORTED;
 }
@@ -1216,18 +1195,14 @@ static void operand_acc(std::vector<Acc>& v, const Operand& o, int di, int dj, i
 }
 
 void mst_plan::accesses(const Step& s, std::vector<Acc>& v, bool scheduled) const {
-    // scheduled: s.first indexes the scheduled (per-clip relocated) descriptor arrays; clip 0's copies equal the originals
-    const std::vector<GemmDesc>& gemms = scheduled ? s_gemms : this->gemms;
-    const std::vector<GatherDesc>& gathers = scheduled ? s_gathers : this->gathers;
-    const std::vector<SegRedDesc>& segreds = scheduled ? s_segreds : this->segreds;
-    const std::vector<LstmDesc>& lstms = scheduled ? s_lstms : this->lstms;
-    const std::vector<CombineDesc>& combines = scheduled ? s_combines : this->combines;
-    const std::vector<NotesDesc>& notes = scheduled ? s_notes : this->notes;
-    const std::vector<RowLinDesc>& rowlins = scheduled ? s_rowlins : this->rowlins;
+    // scheduled: s is a step of a scheduled list, so s.first of a replicated kind indexes the scheduled (per-clip relocated)
+    // descriptors; clip 0's copies equal the originals
+    const bool sc = scheduled && KINDS[s.kind].sched;
+    auto tab = [sc](const auto& t) -> const auto& { return sc ? t.sched : t.host; };
     for (int i = 0; i < s.count; ++i) {
         switch (s.kind) {
         case K_GEMM: case K_GEMM_FOLD: {
-            const GemmDesc& g = gemms[s.first + i];
+            const GemmDesc& g = tab(gemms)[s.first + i];
             const int gk = g.fold_rows ? g.fold_rows : g.K;      // a folded reduction touches, per clip, what one clip's would
             const int gm = g.clip_rows ? 1 : g.M;                // ... and so do clips-as-rows (its scheduled copy has M = clips)
             Operand ga = g.A;
@@ -1245,7 +1220,7 @@ void mst_plan::accesses(const Step& s, std::vector<Acc>& v, bool scheduled) cons
         }
         case K_LIN_F: case K_LIN_A: case K_LIN_W: {
             if (i > 0) break;
-            const LinDesc& l = lins[s.first];
+            const LinDesc& l = lins.host[s.first];
             const int64_t nx = (int64_t)(l.rows - 1) * l.x_ld + l.K, ny = (int64_t)(l.rows - 1) * l.y_ld + l.N;
             if (s.kind == K_LIN_F) { acc_add(v, l.x_space, l.x_off, nx, false); acc_add(v, SP_WS, l.y_off, ny, true); }
             else if (s.kind == K_LIN_W) {
@@ -1259,7 +1234,7 @@ void mst_plan::accesses(const Step& s, std::vector<Acc>& v, bool scheduled) cons
         }
         case K_CONV_P: case K_CONV_F: case K_CONV_W: {
             if (i > 0) break;
-            const ConvDesc& c = convs[s.first];
+            const ConvDesc& c = convs.host[s.first];
             const int64_t n = (int64_t)c.P * c.OC * NOCT;
             if (s.kind == K_CONV_P) acc_add(v, SP_TMP, c.wp_off, (int64_t)NF * 72 * 64, true);
             else if (s.kind == K_CONV_F) { acc_add(v, SP_TMP, c.wp_off, (int64_t)NF * 72 * 64, false); acc_add(v, SP_WS, c.x1_off, n, true); }
@@ -1267,7 +1242,7 @@ void mst_plan::accesses(const Step& s, std::vector<Acc>& v, bool scheduled) cons
             break;
         }
         case K_GATHER: {
-            const GatherDesc& g = gathers[s.first + i];
+            const GatherDesc& g = tab(gathers)[s.first + i];
             for (int q = 0; q < g.nseg; ++q) {
                 const Seg& sg = g.seg[q];
                 int64_t maxrow = 0;
@@ -1278,7 +1253,7 @@ void mst_plan::accesses(const Step& s, std::vector<Acc>& v, bool scheduled) cons
             break;
         }
         case K_SEGRED: {
-            const SegRedDesc& r = segreds[s.first + i];
+            const SegRedDesc& r = tab(segreds)[s.first + i];
             const int64_t rows = (int64_t)r.d[0] * r.d[1] * r.d[2] * r.d[3];
             acc_add(v, SP_GRAD, r.src_off, rows * r.src_ld, false);
             if (r.act != ACT_NONE) acc_add(v, SP_WS, r.y_off, rows * r.src_ld, false);
@@ -1287,13 +1262,13 @@ void mst_plan::accesses(const Step& s, std::vector<Acc>& v, bool scheduled) cons
             break;
         }
         case K_LSTM_T: {
-            const LstmDesc& l = lstms[s.first + i];
+            const LstmDesc& l = tab(lstms)[s.first + i];
             if (l.multi) { acc_add(v, SP_TMP, l.xch_off, 2 * (2 * l.H + 8 * l.H), true); break; }
             if (l.H > 64) acc_add(v, SP_TMP, l.whht_off, (int64_t)4 * l.H * l.H, true);
             break;
         }
         case K_LSTM_F: {
-            const LstmDesc& l = lstms[s.first + i];
+            const LstmDesc& l = tab(lstms)[s.first + i];
             const int64_t n = (int64_t)l.B * l.S;
             acc_add(v, SP_WS, l.zx_off, n * 4 * l.H, false);
             acc_add(v, SP_WS, l.out_off, (n - 1) * l.out_ld + l.H, true);
@@ -1306,7 +1281,7 @@ void mst_plan::accesses(const Step& s, std::vector<Acc>& v, bool scheduled) cons
             break;
         }
         case K_LSTM_B: {
-            const LstmDesc& l = lstms[s.first + i];
+            const LstmDesc& l = tab(lstms)[s.first + i];
             const int64_t n = (int64_t)l.B * l.S;
             acc_add(v, SP_TMP, l.gates_off, n * 4 * l.H, false);
             acc_add(v, SP_TMP, l.c_off, n * l.H, false);
@@ -1316,45 +1291,25 @@ void mst_plan::accesses(const Step& s, std::vector<Acc>& v, bool scheduled) cons
             if (l.multi) acc_add(v, SP_TMP, l.xch_off, 2 * (2 * l.H + 8 * l.H), true);
             break;
         }
-        case K_COMB_F: case K_COMB_B: {
-            const CombineDesc& c = combines[s.first + i];
+        case K_COMB_F: case K_COMB_B: case K_COMB_F1: case K_COMB_F2: case K_COMB_B1: case K_COMB_B2: {
+            // one launch each way, or the halves of a tiled plan (*1 writes the partial sums, *2 reads them back after the exchange)
+            const CombineDesc& c = tab(combines)[s.first + i];
             const int64_t span = (int64_t)(c.Cn - 1) * (c.cs < 0 ? -c.cs : c.cs) + (int64_t)(c.rows - 1) * c.ld + c.cols;
             const int64_t lo = c.cs < 0 ? c.x_off + (int64_t)(c.Cn - 1) * c.cs : c.x_off;
             const int64_t n = (int64_t)c.rows * c.cols;
+            const bool fwd = s.kind == K_COMB_F || s.kind == K_COMB_F1 || s.kind == K_COMB_F2, half2 = s.kind == K_COMB_F2 || s.kind == K_COMB_B2;
             acc_add(v, SP_WS, lo, span, false);
-            acc_add(v, SP_TMP, c.part_off, COMBINE_MAXBLK * (COMBINE_MAXC + 1), true);
-            if (s.kind == K_COMB_F) {
-                acc_add(v, SP_WS, c.out_off, n, true);
-                acc_add(v, SP_TMP, c.stats_off, 64, true);
-            } else {
-                acc_add(v, SP_WS, c.out_off, n, false);
-                acc_add(v, SP_TMP, c.stats_off, 64, false);
-                acc_add(v, SP_GRAD, c.gout_off, n, false);
-                acc_add(v, SP_GRAD, lo - c.x_off + c.gx_off, span, true, true, span == (int64_t)c.Cn * n);
-            }
-            break;
-        }
-        case K_COMB_F1: case K_COMB_F2: case K_COMB_B1: case K_COMB_B2: {
-            const CombineDesc& c = combines[s.first + i];
-            const int64_t span = (int64_t)(c.Cn - 1) * (c.cs < 0 ? -c.cs : c.cs) + (int64_t)(c.rows - 1) * c.ld + c.cols;
-            const int64_t lo = c.cs < 0 ? c.x_off + (int64_t)(c.Cn - 1) * c.cs : c.x_off;
-            const int64_t n = (int64_t)c.rows * c.cols;
-            acc_add(v, SP_WS, lo, span, false);
-            const bool part_w = s.kind == K_COMB_F1 || s.kind == K_COMB_B1;
-            acc_add(v, SP_TMP, c.part_off, COMBINE_MAXBLK * (COMBINE_MAXC + 1), part_w);
-            if (s.kind == K_COMB_F2) { acc_add(v, SP_WS, c.out_off, n, true); acc_add(v, SP_TMP, c.stats_off, 64, true); }
-            if (s.kind == K_COMB_B1 || s.kind == K_COMB_B2) {
-                acc_add(v, SP_WS, c.out_off, n, false);
-                acc_add(v, SP_GRAD, c.gout_off, n, false);
-            }
-            if (s.kind == K_COMB_B2) {
+            acc_add(v, SP_TMP, c.part_off, COMBINE_MAXBLK * (COMBINE_MAXC + 1), !half2);
+            if (fwd && s.kind != K_COMB_F1) { acc_add(v, SP_WS, c.out_off, n, true); acc_add(v, SP_TMP, c.stats_off, 64, true); }
+            if (!fwd) { acc_add(v, SP_WS, c.out_off, n, false); acc_add(v, SP_GRAD, c.gout_off, n, false); }
+            if (!fwd && s.kind != K_COMB_B1) {
                 acc_add(v, SP_TMP, c.stats_off, 64, false);
                 acc_add(v, SP_GRAD, lo - c.x_off + c.gx_off, span, true, true, span == (int64_t)c.Cn * n);
             }
             break;
         }
         case K_COPY_F: case K_COPY_B: {
-            const CopyDesc& c = copies[s.first + i];
+            const CopyDesc& c = copies.host[s.first + i];
             const int64_t ss = (int64_t)(c.na - 1) * c.src_sa + (int64_t)(c.nb - 1) * c.src_sb + c.cols;
             const int64_t ds = (int64_t)(c.na - 1) * c.dst_sa + (int64_t)(c.nb - 1) * c.dst_sb + c.cols;
             if (s.kind == K_COPY_F) { acc_add(v, SP_WS, c.src_off, ss, false); acc_add(v, SP_WS, c.dst_off, ds, true); }
@@ -1362,7 +1317,7 @@ void mst_plan::accesses(const Step& s, std::vector<Acc>& v, bool scheduled) cons
             break;
         }
         case K_FOLD: case K_SPREAD: {
-            const FoldDesc& f = folds[s.first + i];
+            const FoldDesc& f = folds.host[s.first + i];
             const int64_t span = (int64_t)(f.nrows - 1) * f.row_stride + (int64_t)(f.ncols - 1) * f.col_stride + 1;
             acc_add(v, f.space, f.part_off, span, s.kind == K_SPREAD);
             acc_add(v, SP_TMP, f.sum_off, f.ncols, s.kind == K_FOLD);
@@ -1374,7 +1329,7 @@ void mst_plan::accesses(const Step& s, std::vector<Acc>& v, bool scheduled) cons
             break;
         }
         case K_ROW_F: case K_ROW_B: {
-            const RowLinDesc& r = rowlins[s.first + i];
+            const RowLinDesc& r = tab(rowlins)[s.first + i];
             const int64_t nx = (int64_t)r.rows * r.kin, ny = (int64_t)r.rows * r.nout;
             acc_add(v, SP_WS, r.x_off, nx, false);
             acc_add(v, SP_WS, r.y_off, ny, s.kind == K_ROW_F);
@@ -1386,7 +1341,7 @@ void mst_plan::accesses(const Step& s, std::vector<Acc>& v, bool scheduled) cons
             break;
         }
         case K_ME_SQ: case K_ME_F: case K_ME_RED: case K_ME_B: {
-            const NotesDesc& n = notes[s.first + i];
+            const NotesDesc& n = tab(notes)[s.first + i];
             const int64_t rows = (int64_t)n.C * n.Q, mel = (int64_t)n.Q * NF * NPN * n.W;
             const int64_t nparts = (int64_t)(n.C + 1) * n.nwc;
             acc_add(v, SP_WS, n.oct_off, rows * NOCT * n.W, false);
@@ -1411,17 +1366,16 @@ void mst_plan::accesses(const Step& s, std::vector<Acc>& v, bool scheduled) cons
             break;
         }
         case K_PSA_F: case K_PSA_B: {
-            const NotesDesc& n = notes[s.first + i];
-            const bool me = false, bwd = s.kind == K_PSA_B;
+            const NotesDesc& n = tab(notes)[s.first + i];
+            const bool bwd = s.kind == K_PSA_B;
             const int64_t pos = (int64_t)n.C * n.Q * NF * NPN;
-            const int64_t rows = me ? (int64_t)n.C * n.Q : (int64_t)n.C * n.Q * NF;
-            const int ow = me ? NOCT * n.W : NOCT * 30, dw = me ? NDEG * n.W : NDEG * 30, outw = me ? n.W : NPF;
+            const int ow = NOCT * 30, dw = NDEG * 30, outw = NPF;
             const int64_t mln = (int64_t)n.Q * NF * NPN * n.W;            // melody rows (melody_linear is applied inside the kernels)
             acc_add(v, SP_WS, n.rt_oct_off, (int64_t)n.Q * NF * ow, false);
             acc_add(v, SP_WS, n.rt_deg_off, (int64_t)n.Q * NF * dw, false);
             acc_add(v, SP_WS, n.it_oct_off, (int64_t)n.C * ow, false);
             acc_add(v, SP_WS, n.it_deg_off, (int64_t)n.C * dw, false);
-            if (!me) acc_add(v, SP_WS, n.mel_off, mln, false);
+            acc_add(v, SP_WS, n.mel_off, mln, false);
             acc_add(v, SP_WS, n.out_off, pos * outw, !bwd);
             if (bwd) {
                 // (under MST_BF_LOSS_FUSED the upstream gradient is not read; declaring the read keeps the generic path safe)
@@ -1432,7 +1386,7 @@ void mst_plan::accesses(const Step& s, std::vector<Acc>& v, bool scheduled) cons
                 acc_add(v, SP_GRAD, n.itp_deg_off, (int64_t)n.nblk * n.C * dw, true);
                 acc_add(v, SP_GRAD, n.rt_oct_off, (int64_t)n.Q * NF * ow, true);       // channel sums of dL/dz = gradient of rt
                 acc_add(v, SP_GRAD, n.rt_deg_off, (int64_t)n.Q * NF * dw, true);
-                if (!me) acc_add(v, SP_GRAD, n.g_mel_off, mln, true);
+                acc_add(v, SP_GRAD, n.g_mel_off, mln, true);
                 acc_add(v, SP_TMP, n.slab_off, (int64_t)n.slab_stride * n.nblk, true);
             }
             break;
@@ -1464,19 +1418,9 @@ void mst_plan::schedule_pass(const std::vector<Step>& seq, std::vector<Step>& ou
         for (int i = 0; i < n; ++i) {
             if (done[i] || level[i] != lv) continue;
             const Step& s0 = seq[i];
-            const bool mergeable = !opt.no_merge && (s0.kind == K_GEMM || s0.kind == K_GEMM_FOLD || s0.kind == K_GATHER || s0.kind == K_SEGRED || s0.kind == K_LSTM_T ||
-                                   s0.kind == K_LSTM_F || s0.kind == K_LSTM_B || s0.kind == K_COMB_F || s0.kind == K_COMB_B);
+            const KindInfo& ki = KINDS[s0.kind];
+            const bool mergeable = !opt.no_merge && ki.merge, is_lstm = ki.fam == F_LSTM;
             Step m = s0; m.count = 0; m.lvl = lv;
-            const bool is_lstm = s0.kind == K_LSTM_T || s0.kind == K_LSTM_F || s0.kind == K_LSTM_B;
-            const bool is_comb = s0.kind == K_COMB_F || s0.kind == K_COMB_B || (s0.kind >= K_COMB_F1 && s0.kind <= K_COMB_B2);
-            const bool is_notes = s0.kind == K_ME_F || s0.kind == K_ME_B || s0.kind == K_PSA_F || s0.kind == K_PSA_B || s0.kind == K_ME_SQ || s0.kind == K_ME_RED;
-            if (s0.kind == K_GEMM || s0.kind == K_GEMM_FOLD) m.first = (int)s_gemms.size();
-            else if (s0.kind == K_GATHER) m.first = (int)s_gathers.size();
-            else if (s0.kind == K_SEGRED) m.first = (int)s_segreds.size();
-            else if (is_lstm) m.first = (int)s_lstms.size();
-            else if (is_comb) m.first = (int)s_combines.size();
-            else if (is_notes) m.first = (int)s_notes.size();
-            else if (s0.kind == K_ROW_F || s0.kind == K_ROW_B) m.first = (int)s_rowlins.size();
             std::vector<int> members;                       // indices into the per-kind descriptor vectors (one clip)
             for (int j = i; j < n; ++j) {
                 if (done[j] || level[j] != lv) continue;
@@ -1485,7 +1429,7 @@ void mst_plan::schedule_pass(const std::vector<Step>& seq, std::vector<Step>& ou
                 // LSTM launches come in a register-resident (H <= 64) and an L2 flavour
                 if (is_lstm && ((s.b > 64) != (s0.b > 64))) continue;
                 // ... and the multi-workgroup flavour is a kernel of its own (grid and hidden size fixed): never merged with another
-                if (is_lstm && j != i && (lstms[s.first].multi || lstms[s0.first].multi)) continue;
+                if (is_lstm && j != i && (lstms.host[s.first].multi || lstms.host[s0.first].multi)) continue;
                 if (j != i && !mergeable) continue;
                 done[j] = 1;
                 for (int q = 0; q < s.count; ++q) members.push_back(s.first + q);
@@ -1496,63 +1440,57 @@ void mst_plan::schedule_pass(const std::vector<Step>& seq, std::vector<Step>& ou
             // clip-major replication: clip k's copy of every member, relocated to clip k's workspace slices.
             // The W_hh transpose reads parameters only, so it runs once for all clips.
             // (the multi-workgroup flavour's K_LSTM_T step clears per-clip exchange tags instead: one copy per clip)
-            const bool shared_T = s0.kind == K_LSTM_T && !lstms[s0.first].multi;
-            const int copies = (shared_T || s0.kind == K_GEMM_FOLD || s0.kind >= K_CONV_P) ? 1 : K();
-            for (int k = 0; k < copies; ++k) {
-                for (int idx : members) {
-                    if (s0.kind == K_GEMM || s0.kind == K_GEMM_FOLD) {
-                        GemmDesc g = reloc(gemms[idx], k); g.variant = gemm_variant(g);
-                        if (g.fold_rows) {          // arena sizes are final now: clip strides of the folded reduction
-                            g.acs = shift(g.A.space, 1); g.acs2 = (g.A.kind == OPK_ACTGRAD || g.A.kind == OPK_CONVGRAD) ? shift(g.A.space2, 1) : 0; g.bcs = shift(g.B.space, 1);
-                            // the loader adds clip * stride as a 32-bit element offset
-                            if ((uint64_t)std::max(g.acs, std::max(g.acs2, g.bcs)) * (uint64_t)K() > 0xFFFFFFFFull) err = MST_ERR_UNSUPPORTED;
-                        }
-                        if (g.clip_rows) {          // the clips become the rows: row stride = the clip stride of the operand's arena
-                            g.M = K();
-                            if (g.A.kind == OPK_DENSE) g.A.si = shift(g.A.space, 1);
-                            else g.A.ld = (int32_t)shift(g.A.space, 1);              // OPK_ACTGRAD: dY and Y share the stride
-                            g.out.ldc = (int32_t)shift(g.out.space, 1);
-                            if ((uint64_t)act_top * (uint64_t)K() > 0x7FFFFFFFull) err = MST_ERR_UNSUPPORTED;     // 32-bit row offsets
-                        }
-                        const int kr = (g.K + g.ksplit - 1) / g.ksplit;
-                        g.kdsel = kr <= 32 ? 0 : (kr <= 64 ? 1 : 2);
-                        // tiles per workgroup (64x64 tiling): measured on MI355X at 64 clips per launch, runs of 2 / 4 / 8 tiles
-                        // lost 7 / 22 / 33 % against one tile per workgroup (fewer, longer workgroups: worse balance over the
-                        // 256 CUs than the saved per-workgroup latency buys), so the default stays 1; the option remains for experiments
-                        g.run = (mfma && opt.gemm_run > 1) ? opt.gemm_run : 1;
-                        if (g.variant < 0) err = MST_ERR_UNSUPPORTED;
-                        s_gemms.push_back(g);
+            const bool shared_T = s0.kind == K_LSTM_T && !lstms.host[s0.first].multi;
+            const int reps = ki.per_clip && !shared_T ? K() : 1;
+            if (ki.sched)
+                with_sched_table(ki.fam, [&](auto& t) {
+                    m.first = (int)t.sched.size();
+                    for (int k = 0; k < reps; ++k)
+                        for (int idx : members) t.sched.push_back(reloc(t.host[idx], k));
+                });
+            m.count = (int)members.size() * reps;
+            if (ki.fam == F_GEMM) {
+                for (int q = 0; q < m.count; ++q) {
+                    GemmDesc& g = gemms.sched[m.first + q];
+                    g.variant = gemm_variant(g);
+                    if (g.fold_rows) {          // arena sizes are final now: clip strides of the folded reduction
+                        g.acs = shift(g.A.space, 1); g.acs2 = (g.A.kind == OPK_ACTGRAD || g.A.kind == OPK_CONVGRAD) ? shift(g.A.space2, 1) : 0; g.bcs = shift(g.B.space, 1);
+                        // the loader adds clip * stride as a 32-bit element offset
+                        if ((uint64_t)std::max(g.acs, std::max(g.acs2, g.bcs)) * (uint64_t)K() > 0xFFFFFFFFull) err = MST_ERR_UNSUPPORTED;
                     }
-                    else if (s0.kind == K_GATHER) s_gathers.push_back(reloc(gathers[idx], k));
-                    else if (s0.kind == K_SEGRED) s_segreds.push_back(reloc(segreds[idx], k));
-                    else if (is_lstm) s_lstms.push_back(reloc(lstms[idx], k));
-                    else if (is_comb) s_combines.push_back(reloc(combines[idx], k));
-                    else if (is_notes) s_notes.push_back(reloc(notes[idx], k));
-                    else if (s0.kind == K_ROW_F || s0.kind == K_ROW_B) s_rowlins.push_back(reloc(rowlins[idx], k));
+                    if (g.clip_rows) {          // the clips become the rows: row stride = the clip stride of the operand's arena
+                        g.M = K();
+                        if (g.A.kind == OPK_DENSE) g.A.si = shift(g.A.space, 1);
+                        else g.A.ld = (int32_t)shift(g.A.space, 1);              // OPK_ACTGRAD: dY and Y share the stride
+                        g.out.ldc = (int32_t)shift(g.out.space, 1);
+                        if ((uint64_t)act_top * (uint64_t)K() > 0x7FFFFFFFull) err = MST_ERR_UNSUPPORTED;     // 32-bit row offsets
+                    }
+                    const int kr = (g.K + g.ksplit - 1) / g.ksplit;
+                    g.kdsel = kr <= 32 ? 0 : (kr <= 64 ? 1 : 2);
+                    // tiles per workgroup (64x64 tiling): measured on MI355X at 64 clips per launch, runs of 2 / 4 / 8 tiles
+                    // lost 7 / 22 / 33 % against one tile per workgroup (fewer, longer workgroups: worse balance over the
+                    // 256 CUs than the saved per-workgroup latency buys), so the default stays 1; the option remains for experiments
+                    g.run = (mfma && opt.gemm_run > 1) ? opt.gemm_run : 1;
+                    if (g.variant < 0) err = MST_ERR_UNSUPPORTED;
                 }
-            }
-            m.count = (int)members.size() * copies;
-            if (m.kind == K_GEMM || m.kind == K_GEMM_FOLD) {      // flat grid: a clip's block range concatenates its members' (tile, k-split) workgroups
+                // flat grid: a clip's block range concatenates its members' (tile, k-split) workgroups
                 const int nm = (int)members.size();
                 int total = 0;
-                for (int q = 0; q < nm; ++q) {
-                    const GemmDesc& g0 = s_gemms[m.first + q];
-                    for (int k = 0; k < copies; ++k) s_gemms[m.first + k * nm + q].blk_begin = total;
-                    total += gemm_blocks(g0, mfma);
-                }
-                m.a = total; m.b = nm;        // blocks per clip, members per clip
                 m.c = (int)s_gemm_owner.size();
                 for (int q = 0; q < nm; ++q) {
-                    const int nb = gemm_blocks(s_gemms[m.first + q], mfma);
-                    for (int i = 0; i < nb; ++i) s_gemm_owner.push_back(q);
+                    const int nb = gemm_blocks(gemms.sched[m.first + q], mfma);
+                    for (int k = 0; k < reps; ++k) gemms.sched[m.first + k * nm + q].blk_begin = total;
+                    total += nb;
+                    s_gemm_owner.insert(s_gemm_owner.end(), nb, q);
                 }
+                m.a = total; m.b = nm;        // blocks per clip, members per clip
             }
             if (m.kind == K_SEGRED) {    // same flat layout; m.b keeps the stage-2 block count, members = count / clips
                 const int nm = (int)members.size();
                 int total = 0;
                 for (int q = 0; q < nm; ++q) {
-                    const SegRedDesc& r0 = s_segreds[m.first + q];
-                    for (int k = 0; k < copies; ++k) s_segreds[m.first + k * nm + q].blk_begin = total;
+                    const SegRedDesc& r0 = segreds.sched[m.first + q];
+                    for (int k = 0; k < reps; ++k) segreds.sched[m.first + k * nm + q].blk_begin = total;
                     total += (r0.nidx * r0.nchunk * r0.width + 255) / 256;
                 }
                 m.a = total;
@@ -1593,35 +1531,34 @@ void mst_plan::first_writers(std::vector<Step>& list, size_t begin, bool per_sta
     };
     for (const char* nm : {"pitched_pred", "unpitched_pred", "instruments_pred", "mode_pred", "bpm_pred"}) external(nm);
     if (per_stage) for (const char* nm : {"style", "melody", "rhythm"}) external(nm);      // seeded or cleared by the caller
-    const int copies = K();
     for (size_t si = begin; si < list.size(); ++si) {
         Step& m = list[si];
-        const bool plain = m.kind >= K_COPY_F && m.kind != K_GEMM_FOLD;   // indexes an unscheduled (one-clip) descriptor vector
-        const int nm = (m.kind == K_GEMM || m.kind == K_GEMM_FOLD) ? m.b : (plain ? m.count : m.count / copies);
+        // a kind that runs once for all clips has one descriptor per member (K_GEMM_FOLD: one first flag for a clips-as-rows dX)
+        const int reps = KINDS[m.kind].per_clip ? K() : 1, nm = m.count / reps;
         for (int q = 0; q < nm; ++q) {
             std::vector<Acc> acc;
             Step one = m; one.first = m.first + q; one.count = 1;
-            accesses(one, acc, !plain);
+            accesses(one, acc, true);
             for (const Acc& a : acc) {
                 if (a.space != SP_GRAD || a.w) continue;
                 if (!covered(have, a.lo, a.hi)) { Acc z = a; z.w = true; z.space = m.stage; zero.push_back(z); have.push_back(a); }
             }
             int first = 0;
+            bool accum = false;
             for (const Acc& a : acc) {
                 if (a.space != SP_GRAD || !a.w) continue;
                 if (!a.accum) { if (a.dense) have.push_back(a); continue; }      // plain store of a dense range
+                accum = true;
                 if (a.dense && !touches(have, a.lo, a.hi)) { first = 1; have.push_back(a); }
                 else if (!covered(have, a.lo, a.hi)) { Acc z = a; z.space = m.stage; zero.push_back(z); have.push_back(a); }
             }
-            if (m.kind == K_COPY_B) this->copies[m.first + q].first = first;
-            if (m.kind == K_LIN_A) this->lins[m.first + q].first[per_stage ? 0 : 1] = first;
-            for (int k = 0; k < copies && !plain; ++k) {
-                const int idx = m.first + k * nm + q;
-                if (m.kind == K_GEMM) s_gemms[idx].out.first = first;
-                else if (m.kind == K_GEMM_FOLD) { if (k == 0) s_gemms[m.first + q].out.first = first; }      // one descriptor for all clips (clips-as-rows dX)
-                else if (m.kind == K_SEGRED) s_segreds[idx].first = first;
-                else if (m.kind == K_COMB_B || m.kind == K_COMB_B2) s_combines[idx].first = first;
-                else if (m.kind == K_ROW_B) s_rowlins[idx].first = first;
+            if (!accum) continue;                      // the flag belongs to the writers that can accumulate
+            for (int k = 0, idx = m.first + q; k < reps; ++k, idx += nm) {
+                switch (KINDS[m.kind].fam) {
+                case F_GEMM: gemms.sched[idx].out.first = first; break;     case F_SEGRED: segreds.sched[idx].first = first; break;
+                case F_COMB: combines.sched[idx].first = first; break;      case F_ROWLIN: rowlins.sched[idx].first = first; break;
+                case F_COPY: copies.host[idx].first = first; break;         case F_LIN: lins.host[idx].first[per_stage ? 0 : 1] = first; break;
+                }
             }
         }
     }
@@ -1641,7 +1578,7 @@ bool mst_plan::assign_streams(std::vector<Step>& L) {
     for (int i = 0; i < n; ++i) accesses(L[i], acc[i], true);
     auto dur = [&](const Step& st) {           // rough one-clip durations in us (profiles/: pass_timeline_one_clip)
         switch (st.kind) {
-        case K_LSTM_F: case K_LSTM_B: return s_lstms[st.first].multi ? 30.0 : 15.0;
+        case K_LSTM_F: case K_LSTM_B: return lstms.sched[st.first].multi ? 30.0 : 15.0;
         case K_ME_F: case K_ME_B: case K_PSA_F: case K_PSA_B: return 18.0;
         case K_GEMM: case K_GEMM_FOLD: return st.count > 8 ? 10.0 : 5.0;
         case K_SEGRED: return 9.0;
@@ -1724,7 +1661,7 @@ void mst_plan::schedule() {
     // one-clip plans: the exchange tags of the multi-workgroup LSTM ride on the same launch (the scratch arena follows the
     // gradient arena, so a chunk can address it); mst_train_iteration then skips the separate clear
     if (K() == 1)
-        for (const LstmDesc& l : lstms)
+        for (const LstmDesc& l : lstms.host)
             if (l.multi) { zero_all.push_back(ZeroChunk{act_top + l.xch_off, (int32_t)(2 * (2 * l.H + 8 * l.H)), 0}); tags_in_zero = true; }
     if (!tiled()) return;
     // ---- one train iteration of a tiled plan as phases that end at an exchange
@@ -1734,9 +1671,9 @@ void mst_plan::schedule() {
         const int64_t np = (int64_t)P() * NF * NPN, nu = U ? (int64_t)Q() * NF * NUN : 0;
         FoldDesc f{}; f.space = SP_TMP; f.part_off = loss_scratch; f.nrows = loss_blocks(np); f.row_stride = 8; f.ncols = 7; f.col_stride = 1;
         f.sum_off = loss_sum_off;
-        loss_fold[0] = (int)folds.size(); folds.push_back(f);
+        loss_fold[0] = (int)folds.host.size(); folds.host.push_back(f);
         f.part_off = loss_scratch + (mst_loss_scratch_floats() - 64) / 2; f.nrows = U ? loss_blocks(nu) : 1; f.sum_off = loss_sum_off + 8;
-        loss_fold[1] = (int)folds.size(); folds.push_back(f);
+        loss_fold[1] = (int)folds.host.size(); folds.host.push_back(f);
     }
     auto mk = [](int what, int pass, int begin, int end) { Phase ph{}; ph.what = what; ph.pass = pass; ph.begin = begin; ph.end = end; ph.nx = 0; return ph; };
     // An exchange is DEFERRED past every following step that does not touch its range (the list is a valid order, and such a step
@@ -1750,8 +1687,7 @@ void mst_plan::schedule() {
         auto touches_pending = [&](const Step& st) {
             if (!cur.nx) return false;
             std::vector<Acc> acc;
-            const bool plain = st.kind >= K_COPY_F && st.kind != K_GEMM_FOLD;
-            accesses(st, acc, !plain);
+            accesses(st, acc, true);
             for (int q = 0; q < cur.nx; ++q) {
                 const Xchg& x = xchgs[cur.xchg[q]];
                 for (const Acc& a : acc)
@@ -1790,21 +1726,12 @@ extern "C" int32_t mst_debug_slab_columns_disjoint(int64_t off_x, int32_t width_
     return slab_columns_disjoint(off_x, width_x, off_y, width_y, ld) ? 1 : 0;
 }
 
-template <class D>
-static int up(const std::vector<D>& v, D** dev) {
-    *dev = nullptr;
-    if (v.empty()) return 0;
-    if (hipMalloc((void**)dev, v.size() * sizeof(D)) != hipSuccess) return MST_ERR_ALLOC;
-    if (hipMemcpy(*dev, v.data(), v.size() * sizeof(D), hipMemcpyHostToDevice) != hipSuccess) return MST_ERR_ALLOC;
-    return 0;
-}
-
 int mst_plan::upload() {
     int e = 0;
-    e |= up(s_gemms, &d_gemms); e |= up(s_gathers, &d_gathers); e |= up(s_segreds, &d_segreds); e |= up(s_lstms, &d_lstms);
-    e |= up(s_combines, &d_combines); e |= up(s_notes, &d_notes); e |= up(s_rowlins, &d_rowlins);
+    e |= gemms.upload(); e |= gathers.upload(); e |= segreds.upload(); e |= lstms.upload();
+    e |= combines.upload(); e |= notes.upload(); e |= rowlins.upload();
     e |= up(s_gemm_owner, &d_gemm_owner);
-    e |= up(copies, &d_copies); e |= up(folds, &d_folds); e |= up(zero_fwd, &d_zero_fwd);
+    e |= copies.upload(); e |= folds.upload(); e |= up(zero_fwd, &d_zero_fwd);      // (convs and lins go by value)
     for (int st = 0; st < 3; ++st) e |= up(zero_stage[st], &d_zero_stage[st]);
     e |= up(zero_all, &d_zero_all);
     for (int s = 0; s < 3; ++s) {
@@ -1822,26 +1749,16 @@ int mst_plan::upload() {
                 spans.push_back({ent.dst, hi});
                 slabs_all.push_back(ent);
             }
+        // entries whose bounding spans overlap are disjoint only as column blocks of the SAME parameter matrix (same base, same
+        // row pitch) with disjoint column ranges, columns counted from the matrix's own first element
         slabs_all_ok = true;
-        std::vector<std::pair<int64_t, int64_t>> sorted_spans = spans;
-        std::sort(sorted_spans.begin(), sorted_spans.end());
-        for (size_t i = 1; i < sorted_spans.size(); ++i)
-            if (sorted_spans[i].first < sorted_spans[i - 1].second) {
-                // column blocks of one weight matrix interleave inside a bounding span: accept only exact 2-D disjointness
-                slabs_all_ok = false;
+        for (size_t i = 0; i < slabs_all.size() && slabs_all_ok; ++i)
+            for (size_t j = i + 1; j < slabs_all.size() && slabs_all_ok; ++j) {
+                const SlabEntry& x = slabs_all[i]; const SlabEntry& y = slabs_all[j];
+                if (spans[i].second <= spans[j].first || spans[j].second <= spans[i].first) continue;
+                slabs_all_ok = x.width > 0 && y.width > 0 && x.dst_ld == y.dst_ld && x.base == y.base &&
+                               slab_columns_disjoint(x.dst - x.base, x.width, y.dst - y.base, y.width, x.dst_ld);
             }
-        if (!slabs_all_ok) {          // precise check: element sets of 2-D entries (rows of `width` at stride dst_ld)
-            slabs_all_ok = true;
-            for (size_t i = 0; i < slabs_all.size() && slabs_all_ok; ++i)
-                for (size_t j = i + 1; j < slabs_all.size() && slabs_all_ok; ++j) {
-                    const SlabEntry& x = slabs_all[i]; const SlabEntry& y = slabs_all[j];
-                    if (spans[i].second <= spans[j].first || spans[j].second <= spans[i].first) continue;
-                    // overlapping bounding spans: disjoint only if both are column blocks of the SAME parameter matrix (same base,
-                    // same row pitch) with disjoint column ranges, columns counted from the matrix's own first element
-                    if (!(x.width > 0 && y.width > 0 && x.dst_ld == y.dst_ld && x.base == y.base)) { slabs_all_ok = false; break; }
-                    slabs_all_ok = slab_columns_disjoint(x.dst - x.base, x.width, y.dst - y.base, y.width, x.dst_ld);
-                }
-        }
         for (size_t i = 0; i < slabs_all.size(); ++i)
             for (int st = 0; st < slabs_all[i].count; st += 64) slab_blocks_all.push_back(SlabBlock{(int)i, st});
         e |= up(slabs_all, &d_slabs_all);
@@ -1884,9 +1801,10 @@ extern "C" mst_plan* mst_plan_create_ex(const mst_dims* d, const mst_plan_option
 
 extern "C" void mst_plan_destroy(mst_plan* p) {
     if (!p) return;
-    hipFree(p->d_gemm_owner); hipFree(p->d_rowlins); hipFree(p->d_zero_all); hipFree(p->d_copies); hipFree(p->d_folds); hipFree(p->d_zero_fwd);
+    p->gemms.release(); p->gathers.release(); p->segreds.release(); p->lstms.release(); p->combines.release(); p->notes.release();
+    p->rowlins.release(); p->copies.release(); p->folds.release();
+    hipFree(p->d_gemm_owner); hipFree(p->d_zero_all); hipFree(p->d_zero_fwd);
     for (int st = 0; st < 3; ++st) hipFree(p->d_zero_stage[st]);
-    hipFree(p->d_gemms); hipFree(p->d_gathers); hipFree(p->d_segreds); hipFree(p->d_lstms); hipFree(p->d_combines); hipFree(p->d_notes);
     for (int s = 0; s < 3; ++s) { hipFree(p->d_slabs[s]); hipFree(p->d_slab_blocks[s]); }
     hipFree(p->d_slabs_all); hipFree(p->d_slab_blocks_all);
     for (mst_plan::SideSet& q : p->sides) {
@@ -1940,41 +1858,41 @@ static Bases make_bases(const mst_plan* p, const float* params, float* gparams, 
 
 static int run_step(const mst_plan* p, const Step& s, const Bases& b, hipStream_t st) {
     switch (s.kind) {
-    case K_GEMM: case K_GEMM_FOLD: return launch_gemm(p->d_gemms + s.first, p->d_gemm_owner + s.c, s.b, s.a, s.count / s.b, p->mfma, b, st);
-    case K_GATHER: return launch_gather(p->d_gathers + s.first, s.count, s.a, b, st);
-    case K_SEGRED: return launch_segred(p->d_segreds + s.first, s.count / p->K(), s.a, p->K(), s.b, b, st);
-    case K_LSTM_T: return launch_lstm_transpose(p->d_lstms + s.first, s.count, s.b, p->s_lstms[s.first].multi, b, st);
-    case K_LSTM_F: return launch_lstm_fwd(p->d_lstms + s.first, s.count, s.a, s.b, p->s_lstms[s.first].multi, b, st);
-    case K_LSTM_B: return launch_lstm_bwd(p->d_lstms + s.first, s.count, s.a, s.b, p->s_lstms[s.first].multi, b, st);
-    case K_COMB_F: return launch_combine_fwd(p->d_combines + s.first, s.count, s.a, s.b == 0 ? (p->d.C <= 4 ? 2 : 1) : 0, b, st);
-    case K_COMB_B: return launch_combine_bwd(p->d_combines + s.first, s.count, s.a, s.b == 0 ? (p->d.C <= 4 ? 2 : 1) : 0, b, st);
-    case K_COMB_F1: return launch_combine_phase(p->d_combines + s.first, s.a, 0, b, st);
-    case K_COMB_F2: return launch_combine_phase(p->d_combines + s.first, s.a, 1, b, st);
-    case K_COMB_B1: return launch_combine_phase(p->d_combines + s.first, s.a, 2, b, st);
-    case K_COMB_B2: return launch_combine_phase(p->d_combines + s.first, s.a, 3, b, st);
-    case K_COPY_F: return launch_copy_rows(p->d_copies + s.first, p->copies[s.first], 0, b, st);
-    case K_COPY_B: return launch_copy_rows(p->d_copies + s.first, p->copies[s.first], 1, b, st);
-    case K_FOLD: return launch_fold(p->d_folds + s.first, 0, b, st);
-    case K_SPREAD: return launch_fold(p->d_folds + s.first, 1, b, st);
+    case K_GEMM: case K_GEMM_FOLD: return launch_gemm(p->gemms.dev + s.first, p->d_gemm_owner + s.c, s.b, s.a, s.count / s.b, p->mfma, b, st);
+    case K_GATHER: return launch_gather(p->gathers.dev + s.first, s.count, s.a, b, st);
+    case K_SEGRED: return launch_segred(p->segreds.dev + s.first, s.count / p->K(), s.a, p->K(), s.b, b, st);
+    case K_LSTM_T: return launch_lstm_transpose(p->lstms.dev + s.first, s.count, s.b, p->lstms.sched[s.first].multi, b, st);
+    case K_LSTM_F: return launch_lstm_fwd(p->lstms.dev + s.first, s.count, s.a, s.b, p->lstms.sched[s.first].multi, b, st);
+    case K_LSTM_B: return launch_lstm_bwd(p->lstms.dev + s.first, s.count, s.a, s.b, p->lstms.sched[s.first].multi, b, st);
+    case K_COMB_F: return launch_combine_fwd(p->combines.dev + s.first, s.count, s.a, s.b == 0 ? (p->d.C <= 4 ? 2 : 1) : 0, b, st);
+    case K_COMB_B: return launch_combine_bwd(p->combines.dev + s.first, s.count, s.a, s.b == 0 ? (p->d.C <= 4 ? 2 : 1) : 0, b, st);
+    case K_COMB_F1: return launch_combine_phase(p->combines.dev + s.first, s.a, 0, b, st);
+    case K_COMB_F2: return launch_combine_phase(p->combines.dev + s.first, s.a, 1, b, st);
+    case K_COMB_B1: return launch_combine_phase(p->combines.dev + s.first, s.a, 2, b, st);
+    case K_COMB_B2: return launch_combine_phase(p->combines.dev + s.first, s.a, 3, b, st);
+    case K_COPY_F: return launch_copy_rows(p->copies.dev + s.first, p->copies.host[s.first], 0, b, st);
+    case K_COPY_B: return launch_copy_rows(p->copies.dev + s.first, p->copies.host[s.first], 1, b, st);
+    case K_FOLD: return launch_fold(p->folds.dev + s.first, 0, b, st);
+    case K_SPREAD: return launch_fold(p->folds.dev + s.first, 1, b, st);
     case K_XCHG: return MST_ERR_UNSUPPORTED;        // a tiled plan runs through mst_tiled_phase, which stops at exchanges
     case K_LIN_F: case K_LIN_A: case K_LIN_W: {
-        LinDesc l = p->lins[s.first];
+        LinDesc l = p->lins.host[s.first];
         l.x_cs = p->shift(l.x_space, 1); l.y_cs = p->act_top; l.gx_cs = p->act_top;
         if (s.kind == K_LIN_F) return launch_lin_fwd(l, b, st);
         if (s.kind == K_LIN_W) return launch_lin_dw(l, b, st);
         return launch_lin_dx(l, b, l.first[(b.flags & MST_BF_ALL_STAGES) ? 1 : 0], st);
     }
-    case K_CONV_P: { ConvDesc c = p->convs[s.first]; c.clip_stride = p->act_top; return launch_conv_prep(c, b, st); }
-    case K_CONV_F: { ConvDesc c = p->convs[s.first]; c.clip_stride = p->act_top; return launch_conv_fwd(c, b, st); }
-    case K_CONV_W: { ConvDesc c = p->convs[s.first]; c.clip_stride = p->act_top; return launch_conv_dw(c, b, st); }
-    case K_ROW_F: return launch_rowlin_fwd(p->d_rowlins + s.first, p->s_rowlins[s.first], s.count, b, st);
-    case K_ROW_B: return launch_rowlin_bwd(p->d_rowlins + s.first, p->s_rowlins[s.first], s.count, b, st);
-    case K_ME_SQ: return launch_me_sumsq(p->d_notes + s.first, p->s_notes[s.first], s.count, b, st);
-    case K_ME_RED: return launch_me_bwd_reduce(p->d_notes + s.first, p->s_notes[s.first], s.count, b, st);
-    case K_ME_F: return launch_me_notes_fwd(p->d_notes + s.first, p->s_notes[s.first], s.count, b, st);
-    case K_ME_B: return launch_me_notes_bwd(p->d_notes + s.first, p->s_notes[s.first], s.count, b, st);
-    case K_PSA_F: return launch_psa_notes_fwd(p->d_notes + s.first, p->s_notes[s.first], s.count, b, st);
-    case K_PSA_B: return launch_psa_notes_bwd(p->d_notes + s.first, p->s_notes[s.first], s.count, b, st);
+    case K_CONV_P: { ConvDesc c = p->convs.host[s.first]; c.clip_stride = p->act_top; return launch_conv_prep(c, b, st); }
+    case K_CONV_F: { ConvDesc c = p->convs.host[s.first]; c.clip_stride = p->act_top; return launch_conv_fwd(c, b, st); }
+    case K_CONV_W: { ConvDesc c = p->convs.host[s.first]; c.clip_stride = p->act_top; return launch_conv_dw(c, b, st); }
+    case K_ROW_F: return launch_rowlin_fwd(p->rowlins.dev + s.first, p->rowlins.sched[s.first], s.count, b, st);
+    case K_ROW_B: return launch_rowlin_bwd(p->rowlins.dev + s.first, p->rowlins.sched[s.first], s.count, b, st);
+    case K_ME_SQ: return launch_me_sumsq(p->notes.dev + s.first, p->notes.sched[s.first], s.count, b, st);
+    case K_ME_RED: return launch_me_bwd_reduce(p->notes.dev + s.first, p->notes.sched[s.first], s.count, b, st);
+    case K_ME_F: return launch_me_notes_fwd(p->notes.dev + s.first, p->notes.sched[s.first], s.count, b, st);
+    case K_ME_B: return launch_me_notes_bwd(p->notes.dev + s.first, p->notes.sched[s.first], s.count, b, st);
+    case K_PSA_F: return launch_psa_notes_fwd(p->notes.dev + s.first, p->notes.sched[s.first], s.count, b, st);
+    case K_PSA_B: return launch_psa_notes_bwd(p->notes.dev + s.first, p->notes.sched[s.first], s.count, b, st);
     }
     return MST_ERR_ARG;
 }
@@ -1985,7 +1903,7 @@ static int run_pass(const mst_plan* p, const std::vector<Step>& list, int mask, 
     if (mask == MST_STAGE_ALL) b.flags |= MST_BF_ALL_STAGES;            // p->list(mask, .) is the whole-model list then
     auto runs = [&](const Step& s) {
         if (!(s.stage & mask)) return false;
-        if (tags_cleared && s.kind == K_LSTM_T && p->s_lstms[s.first].multi) return false;     // its only job was the clear
+        if (tags_cleared && s.kind == K_LSTM_T && p->lstms.sched[s.first].multi) return false;     // its only job was the clear
         return true;
     };
     // Streams (plans with `branches`, whole-model lists): launch s goes to stream s.chain (0 = the caller's, c = side stream c - 1)
@@ -2153,9 +2071,9 @@ extern "C" int32_t mst_tiled_phase(const mst_plan* p, int32_t phase, const float
         int e = loss_fwd_partials(ws + at("pitched_pred"), pitched, np, U ? ws + at("unpitched_pred") : nullptr, U ? unpitched : nullptr, nu,
                                   lscratch, st);
         if (e) return e;
-        if (launch_fold(p->d_folds + p->loss_fold[0], 0, b, st) || (U && launch_fold(p->d_folds + p->loss_fold[1], 0, b, st))) return MST_ERR_LAUNCH;
+        if (launch_fold(p->folds.dev + p->loss_fold[0], 0, b, st) || (U && launch_fold(p->folds.dev + p->loss_fold[1], 0, b, st))) return MST_ERR_LAUNCH;
     } else {
-        if (launch_fold(p->d_folds + p->loss_fold[0], 1, b, st) || (U && launch_fold(p->d_folds + p->loss_fold[1], 1, b, st))) return MST_ERR_LAUNCH;
+        if (launch_fold(p->folds.dev + p->loss_fold[0], 1, b, st) || (U && launch_fold(p->folds.dev + p->loss_fold[1], 1, b, st))) return MST_ERR_LAUNCH;
         int e = loss_fwd_tail(np, nu, U ? 1 : 0, ws + at("instruments_pred"), ws + at("used_instruments"), p->z.NI, ws + at("mode_pred"),
                               ws + at("mode"), ws + at("bpm_pred"), ws + at("bpm_target"), 1, ws + p->t_losses.off, ws + p->t_saved.off,
                               lscratch, st, ws + p->t_gl.off, losses);
@@ -2185,23 +2103,23 @@ static void step_cost(const mst_plan* p, const Step& s, double* flops, double* b
     switch (s.kind) {
     case K_GEMM: case K_GEMM_FOLD:
         for (int i = 0; i < s.count; ++i) {
-            const GemmDesc& g = p->s_gemms[s.first + i];
+            const GemmDesc& g = p->gemms.sched[s.first + i];
             f += 2.0 * g.M * g.N * g.K;
             b += 4.0 * ((double)g.M * g.K + (double)g.K * g.N + (double)g.M * g.N);
         }
         break;
     case K_GATHER:
-        for (int i = 0; i < s.count; ++i) { const GatherDesc& g = p->s_gathers[s.first + i]; b += 8.0 * g.rows * g.K; }
+        for (int i = 0; i < s.count; ++i) { const GatherDesc& g = p->gathers.sched[s.first + i]; b += 8.0 * g.rows * g.K; }
         break;
     case K_LIN_F: case K_LIN_A: case K_LIN_W: {
-        const LinDesc& l = p->lins[s.first];
+        const LinDesc& l = p->lins.host[s.first];
         const double rows = (double)l.clips * l.rows;
         f = 2.0 * rows * l.N * l.K;
         b = 4.0 * (rows * l.K + rows * l.N * (s.kind == K_LIN_F ? 1.0 : 2.0) + (double)l.N * l.K);
         break;
     }
     case K_CONV_F: case K_CONV_W: {
-        const ConvDesc& c = p->convs[s.first];
+        const ConvDesc& c = p->convs.host[s.first];
         const double rows = (double)c.clips * c.P * NOCT, kk = NF * NPF * CONV_K;
         f = 2.0 * rows * c.OC * kk;
         b = 4.0 * (rows / NOCT * NF * NPN * NPF + rows * c.OC * (s.kind == K_CONV_F ? 1.0 : 2.0) + c.OC * kk);
@@ -2209,21 +2127,21 @@ static void step_cost(const mst_plan* p, const Step& s, double* flops, double* b
     }
     case K_SEGRED:
         for (int i = 0; i < s.count; ++i) {
-            const SegRedDesc& r = p->s_segreds[s.first + i];
+            const SegRedDesc& r = p->segreds.sched[s.first + i];
             const double rows = (double)r.d[0] * r.d[1] * r.d[2] * r.d[3];
             f += rows * r.width; b += 4.0 * (rows * r.width + 2.0 * r.nidx * r.width);
         }
         break;
     case K_LSTM_F: case K_LSTM_B:
         for (int i = 0; i < s.count; ++i) {
-            const LstmDesc& l = p->s_lstms[s.first + i];
+            const LstmDesc& l = p->lstms.sched[s.first + i];
             f += (double)l.B * l.S * (8.0 * l.H * l.H + 30.0 * l.H);
             b += 4.0 * ((double)l.B * l.S * 11.0 * l.H + 4.0 * l.H * l.H);
         }
         break;
     case K_COMB_F: case K_COMB_B:
         for (int i = 0; i < s.count; ++i) {
-            const CombineDesc& c = p->s_combines[s.first + i];
+            const CombineDesc& c = p->combines.sched[s.first + i];
             const double n = (double)c.rows * c.cols;
             f += n * c.Cn * (s.kind == K_COMB_F ? 4.0 : 8.0);
             b += 4.0 * n * (s.kind == K_COMB_F ? 2.0 * c.Cn + 1 : 4.0 * c.Cn + 2);
@@ -2231,7 +2149,7 @@ static void step_cost(const mst_plan* p, const Step& s, double* flops, double* b
         break;
     case K_ROW_F: case K_ROW_B:
         for (int i = 0; i < s.count; ++i) {
-            const RowLinDesc& r = p->s_rowlins[s.first + i];
+            const RowLinDesc& r = p->rowlins.sched[s.first + i];
             const double mm = 2.0 * r.rows * r.kin * r.nout;
             f += s.kind == K_ROW_F ? mm : 2.0 * mm;
             b += 4.0 * r.rows * (s.kind == K_ROW_F ? r.kin + r.nout : 2.0 * r.kin + 2.0 * r.nout + (r.xgrad ? r.kin : 0));
@@ -2239,7 +2157,7 @@ static void step_cost(const mst_plan* p, const Step& s, double* flops, double* b
         break;
     case K_ME_SQ: case K_ME_F: case K_ME_RED: case K_ME_B: {
         // algorithmic = the reference's (unfused) shapes; the recomputation the fused kernels do on top is not counted
-        const NotesDesc& n = p->s_notes[s.first];
+        const NotesDesc& n = p->notes.sched[s.first];
         const double pos = (double)n.C * n.Q * NF * NPN * s.count, mel = pos / n.C * n.W;
         const double per = 2.0 * n.W + 2.0 * n.CW * NPF + 2.0 * n.W * (n.W + n.CW);
         if (s.kind == K_ME_SQ) { f = pos * (per + 2.0 * n.W); b = 4.0 * pos * NPF; }
@@ -2249,7 +2167,7 @@ static void step_cost(const mst_plan* p, const Step& s, double* flops, double* b
         break;
     }
     case K_PSA_F: case K_PSA_B: {
-        const NotesDesc& n = p->s_notes[s.first];
+        const NotesDesc& n = p->notes.sched[s.first];
         const double pos = (double)n.C * n.Q * NF * NPN * s.count;
         const double per = 2.0 * 30 + 2.0 * NPF * (30 + n.ML);
         f = pos * per * (s.kind == K_PSA_F ? 1.0 : 3.0);
@@ -2286,12 +2204,12 @@ extern "C" int32_t mst_plan_step_info(const mst_plan* p, int32_t mask, int32_t b
     for (const Step* s : steps) {
         int32_t* o = info + 8 * idx++;
         o[0] = o[1] = o[2] = o[3] = 0; o[4] = s->count; o[5] = s->kind; o[6] = s->lvl; o[7] = s->chain;
-        if (s->kind == K_GEMM || s->kind == K_GEMM_FOLD) { const GemmDesc& g = p->s_gemms[s->first]; o[0] = g.M; o[1] = g.N; o[2] = g.K; o[3] = g.ksplit; }
-        else if (s->kind >= K_LIN_F && s->kind <= K_LIN_W) { const LinDesc& l = p->lins[s->first]; o[0] = l.rows; o[1] = l.N; o[2] = l.K; o[3] = l.splits; }
-        else if (s->kind == K_LSTM_F || s->kind == K_LSTM_B) { const LstmDesc& l = p->s_lstms[s->first]; o[0] = l.B; o[1] = l.S; o[2] = l.H; o[3] = l.multi; }
-        else if (s->kind == K_GATHER) { const GatherDesc& g = p->s_gathers[s->first]; o[0] = g.rows; o[1] = g.K; o[2] = g.nseg; }
-        else if (s->kind == K_SEGRED) { const SegRedDesc& r = p->s_segreds[s->first]; o[0] = s->a; o[1] = r.width; o[2] = r.d[0] * r.d[1] * r.d[2] * r.d[3]; }
-        else if (s->kind == K_COMB_F || s->kind == K_COMB_B) { const CombineDesc& c = p->s_combines[s->first]; o[0] = c.Cn; o[1] = c.rows; o[2] = c.cols; o[3] = c.nblk; }
+        if (s->kind == K_GEMM || s->kind == K_GEMM_FOLD) { const GemmDesc& g = p->gemms.sched[s->first]; o[0] = g.M; o[1] = g.N; o[2] = g.K; o[3] = g.ksplit; }
+        else if (KINDS[s->kind].fam == F_LIN) { const LinDesc& l = p->lins.host[s->first]; o[0] = l.rows; o[1] = l.N; o[2] = l.K; o[3] = l.splits; }
+        else if (s->kind == K_LSTM_F || s->kind == K_LSTM_B) { const LstmDesc& l = p->lstms.sched[s->first]; o[0] = l.B; o[1] = l.S; o[2] = l.H; o[3] = l.multi; }
+        else if (s->kind == K_GATHER) { const GatherDesc& g = p->gathers.sched[s->first]; o[0] = g.rows; o[1] = g.K; o[2] = g.nseg; }
+        else if (s->kind == K_SEGRED) { const SegRedDesc& r = p->segreds.sched[s->first]; o[0] = s->a; o[1] = r.width; o[2] = r.d[0] * r.d[1] * r.d[2] * r.d[3]; }
+        else if (s->kind == K_COMB_F || s->kind == K_COMB_B) { const CombineDesc& c = p->combines.sched[s->first]; o[0] = c.Cn; o[1] = c.rows; o[2] = c.cols; o[3] = c.nblk; }
     }
     return idx;
 }
@@ -2306,7 +2224,7 @@ extern "C" int32_t mst_plan_step_gemms(const mst_plan* p, int32_t mask, int32_t 
         if (s.kind != K_GEMM && s.kind != K_GEMM_FOLD) return 0;
         int n = 0;
         for (int q = 0; q < s.b && n < cap; ++q, ++n) {
-            const GemmDesc& g = p->s_gemms[s.first + q];
+            const GemmDesc& g = p->gemms.sched[s.first + q];
             int32_t* o = out + 6 * n;
             o[0] = g.M; o[1] = g.N; o[2] = g.K; o[3] = g.ksplit; o[4] = g.fold_rows; o[5] = gemm_blocks(g, p->mfma);
         }
