@@ -8,7 +8,8 @@
 // ahead so a step costs two barriers and no exposed memory latency.  H > 64 (StyleEncoder,
 // H = 192, 590 KB of W_hh — more than one CU's registers + LDS): one lane per gate row over W_hh^T (
 // transposed once per forward so the per-step L2 reads are lane-contiguous); every in-loop barrier
-// is LDS-only (MST_LDS_BARRIER), so streamed stores / prefetches never stall a step.
+// is LDS-only (MST_LDS_BARRIER), so streamed stores / prefetches never stall a step.  H > 256 (wide bar / style widths, up to
+// 1024): the same over 1024 lanes with several gate rows per lane.  A launch never mixes the three bands (lstm_band).
 #include "mst_common.h"
 
 #define LSTM_ZS 8192        // floats of LDS holding staged per-step operands in the register flavours
@@ -310,6 +311,173 @@ __global__ __launch_bounds__(REG ? 256 : 1024) void lstm_bwd_kernel(const LstmDe
         MST_LDS_BARRIER();
     }
 #undef LSTM_LOAD
+}
+
+// ---- wide flavour (LSTM_L2H < H <= LSTM_WH) -------------------------------------------------------
+// One 1024-lane workgroup per sequence, as the L2 flavour above but with several gate rows per lane.  W_hh (1.6 MB at H = 320,
+// 16 MB at H = 1024: beyond an XCD's L2) is re-read from L2 / the Infinity Cache every step; h_{t-1} / dz_t and the step's
+// matvec results are broadcast through LDS (20 KB at H = 1024); every in-loop barrier is LDS-only and all streamed loads /
+// stores go through global-address-space pointers, so a barrier never drains them.  Summation orders are fixed (no atomics):
+// two runs are bit-identical.  H need not be a multiple of anything: the k (forward) / j (backward) ranges are padded to a
+// multiple of 16 with zero LDS operands and clamped weight rows.
+typedef float lstm_f4 __attribute__((ext_vector_type(4)));
+
+// Forward: lane l < H owns the four consecutive gate rows 4l .. 4l + 3 and reads them as ONE 16-byte load per k from W_hh^T
+// (rows of 4H floats: 16-byte aligned for any H).  k runs in four quarters that advance together (16 loads in flight per lane);
+// row j's z = (q0 + q1) + (q2 + q3), each quarter summed in k order.
+__global__ __launch_bounds__(1024) void lstm_fwd_wide_kernel(const LstmDesc* __restrict__ descs, Bases b) {
+    const LstmDesc d = descs[blockIdx.y];        // by value: no descriptor re-reads after the per-step barriers
+    const int bi = blockIdx.x;
+    if (bi >= d.B) return;
+    const int H = d.H, G = 4 * d.H, tid = threadIdx.x;
+    const int KQ = ((H + 15) & ~15) / 4;        // quarter length, a multiple of 4; h_s is zero beyond H
+    __shared__ __attribute__((aligned(16))) float h_s[LSTM_WH];
+    __shared__ __attribute__((aligned(16))) float z_s[4 * LSTM_WH];
+    const MST_GLOBAL_AS float* zx = (const MST_GLOBAL_AS float*)(b.p[SP_WS] + d.zx_off) + (int64_t)bi * d.S * G;
+    const MST_GLOBAL_AS lstm_f4* wt = (const MST_GLOBAL_AS lstm_f4*)(b.p[SP_TMP] + d.whht_off) + tid;      // W_hh^T row k: wt[k * H]
+    MST_GLOBAL_AS float* ws = (MST_GLOBAL_AS float*)b.p[SP_WS];
+    MST_GLOBAL_AS float* tmp = (MST_GLOBAL_AS float*)b.p[SP_TMP];
+    float bias[4] = {0.f, 0.f, 0.f, 0.f}, zq[4] = {0.f, 0.f, 0.f, 0.f};
+    const int s0 = d.reverse ? d.S - 1 : 0;
+    if (tid < H) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            bias[q] = b.p[SP_PAR][d.bhh_off + q * H + tid];
+            zq[q] = zx[(int64_t)s0 * G + q * H + tid];
+        }
+    }
+    h_s[tid] = 0.f;                              // blockDim = LSTM_WH
+    float c = 0.f;
+    for (int step = 0; step < d.S; ++step) {
+        const int s = d.reverse ? d.S - 1 - step : step;
+        const int64_t row = (int64_t)bi * d.S + s;
+        float zn[4] = {0.f, 0.f, 0.f, 0.f};
+        if (tid < H && step + 1 < d.S) {         // next step's zx row: in flight under this step's matvec
+            const int sn = d.reverse ? s - 1 : s + 1;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) zn[q] = zx[(int64_t)sn * G + q * H + tid];
+        }
+        MST_LDS_BARRIER();
+        if (tid < H) {
+            float a[4][4];                       // [quarter][row 4 * tid + r]
+#pragma unroll
+            for (int qq = 0; qq < 4; ++qq) { a[qq][0] = 0.f; a[qq][1] = 0.f; a[qq][2] = 0.f; a[qq][3] = 0.f; }
+            for (int k = 0; k < KQ; k += 4) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+#pragma unroll
+                    for (int qq = 0; qq < 4; ++qq) {
+                        const int kk = qq * KQ + k + i;
+                        const lstm_f4 w4 = wt[min(kk, H - 1) * H];
+                        const float hv = h_s[kk];
+                        a[qq][0] = fmaf(w4.x, hv, a[qq][0]); a[qq][1] = fmaf(w4.y, hv, a[qq][1]);
+                        a[qq][2] = fmaf(w4.z, hv, a[qq][2]); a[qq][3] = fmaf(w4.w, hv, a[qq][3]);
+                    }
+                }
+            }
+            lstm_f4 z4;
+            z4.x = (a[0][0] + a[1][0]) + (a[2][0] + a[3][0]); z4.y = (a[0][1] + a[1][1]) + (a[2][1] + a[3][1]);
+            z4.z = (a[0][2] + a[1][2]) + (a[2][2] + a[3][2]); z4.w = (a[0][3] + a[1][3]) + (a[2][3] + a[3][3]);
+            reinterpret_cast<lstm_f4*>(z_s)[tid] = z4;
+        }
+        MST_LDS_BARRIER();
+        if (tid < H) {
+            const float ig = sigm(z_s[tid] + zq[0] + bias[0]), fg = sigm(z_s[H + tid] + zq[1] + bias[1]);
+            const float gg = tanh_fast(z_s[2 * H + tid] + zq[2] + bias[2]), og = sigm(z_s[3 * H + tid] + zq[3] + bias[3]);
+            tmp[d.hprev_off + row * H + tid] = h_s[tid];
+            c = fg * c + ig * gg;
+            const float tc = tanh_fast(c);
+            const float h = og * tc;
+            tmp[d.tc_off + row * H + tid] = tc;
+            MST_GLOBAL_AS float* g = tmp + d.gates_off + row * G;
+            g[tid] = ig; g[H + tid] = fg; g[2 * H + tid] = gg; g[3 * H + tid] = og;
+            tmp[d.c_off + row * H + tid] = c;
+            ws[d.out_off + row * d.out_ld + tid] = h;
+            h_s[tid] = h;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) zq[q] = zn[q];
+        }
+    }
+}
+
+// Backward: dh_{t-1}[k] = sum_j W_hh[j, k] dz_t[j].  Lane (part, kk) reads column kk of W_hh (coalesced along kk) over the
+// part's CH contiguous gate rows, in four chunks that advance together; the P = 1024 / HP partial sums of a unit (HP = H rounded up
+// to a wave) are added in part order by the next step.
+__global__ __launch_bounds__(1024) void lstm_bwd_wide_kernel(const LstmDesc* __restrict__ descs, Bases b) {
+    const LstmDesc d = descs[blockIdx.y];        // by value: no descriptor re-reads after the per-step barriers
+    const int bi = blockIdx.x;
+    if (bi >= d.B) return;
+    const int H = d.H, G = 4 * d.H, tid = threadIdx.x;
+    const int HP = (H + 63) & ~63, P = LSTM_WH / HP;              // P <= 3: H > 256
+    const int CH = ((G + P - 1) / P + 15) & ~15, CQ = CH / 4;     // P * CH < G + 64
+    const int kk = tid % HP, part = tid / HP;
+    // dz_t, zero beyond G (the padded rows of the last part); partial sums: part p of unit k at p * H + k
+    __shared__ float dz_s[4 * LSTM_WH + 64];
+    __shared__ float red_s[LSTM_WH];
+    const MST_GLOBAL_AS float* whh = (const MST_GLOBAL_AS float*)(b.p[SP_PAR] + d.whh_off);
+    const MST_GLOBAL_AS float* tmp = (const MST_GLOBAL_AS float*)b.p[SP_TMP];
+    MST_GLOBAL_AS float* gr = (MST_GLOBAL_AS float*)b.p[SP_GRAD];
+    for (int i = tid; i < 4 * LSTM_WH + 64; i += LSTM_WH) dz_s[i] = 0.f;
+    red_s[tid] = 0.f;
+    // streamed operands of a step (saved gates, tanh(c_t), c_{t-1}, incoming gradient), prefetched one step ahead
+    auto load = [&](const int step, float* dst) {
+        const int s_ = d.reverse ? d.S - 1 - step : step;
+        const int sp_ = d.reverse ? s_ + 1 : s_ - 1;
+        const int64_t row_ = (int64_t)bi * d.S + s_;
+        const MST_GLOBAL_AS float* g_ = tmp + d.gates_off + row_ * G;
+        dst[0] = g_[tid]; dst[1] = g_[H + tid]; dst[2] = g_[2 * H + tid]; dst[3] = g_[3 * H + tid];
+        dst[4] = tmp[d.tc_off + row_ * H + tid];
+        dst[5] = step > 0 ? tmp[d.c_off + ((int64_t)bi * d.S + sp_) * H + tid] : 0.f;
+        dst[6] = gr[d.gout_off + row_ * d.out_ld + tid];
+    };
+    float sv[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (tid < H) load(d.S - 1, sv);
+    float dc_next = 0.f;
+    __syncthreads();
+    for (int step = d.S - 1; step >= 0; --step) {
+        const int s = d.reverse ? d.S - 1 - step : step;
+        const int64_t row = (int64_t)bi * d.S + s;
+        float nx[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (tid < H) {
+            if (step > 0) load(step - 1, nx);
+            const float ig = sv[0], fg = sv[1], gg = sv[2], og = sv[3], tc = sv[4], cprev = sv[5];
+            float dhr = red_s[tid];
+            for (int p = 1; p < P; ++p) dhr += red_s[p * H + tid];
+            const float dh = sv[6] + dhr;
+            const float dc = dc_next + dh * og * (1.f - tc * tc);
+            const float dzi = dc * gg * ig * (1.f - ig);
+            const float dzf = dc * cprev * fg * (1.f - fg);
+            const float dzg = dc * ig * (1.f - gg * gg);
+            const float dzo = dh * tc * og * (1.f - og);
+            dc_next = dc * fg;
+            dz_s[tid] = dzi; dz_s[H + tid] = dzf; dz_s[2 * H + tid] = dzg; dz_s[3 * H + tid] = dzo;
+            MST_GLOBAL_AS float* gz = gr + d.gzx_off + row * G;
+            gz[tid] = dzi; gz[H + tid] = dzf; gz[2 * H + tid] = dzg; gz[3 * H + tid] = dzo;
+        }
+        if (step == 0) break;                    // dh_{-1} feeds nothing
+        MST_LDS_BARRIER();
+        if (part < P && kk < H) {                // the gate lanes' reads of red_s ended before the barrier above
+            const MST_GLOBAL_AS float* wc = whh + kk;              // W_hh row j: wc[j * H]
+            const int j0 = part * CH;
+            float a[4] = {0.f, 0.f, 0.f, 0.f};
+            for (int i = 0; i < CQ; i += 4) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+#pragma unroll
+                    for (int cq = 0; cq < 4; ++cq) {
+                        const int j = j0 + cq * CQ + i + u;
+                        a[cq] = fmaf(wc[min(j, G - 1) * H], dz_s[j], a[cq]);
+                    }
+                }
+            }
+            red_s[part * H + kk] = (a[0] + a[1]) + (a[2] + a[3]);
+        }
+        if (tid < H) {
+#pragma unroll
+            for (int q = 0; q < 7; ++q) sv[q] = nx[q];     // the prefetch landed under the matvec above
+        }
+        MST_LDS_BARRIER();
+    }
 }
 
 // ---- grouped flavour ---------------------------------------------------------------------------
@@ -716,7 +884,8 @@ int lstm_multi_blocks_per_cu() {
 #endif
 }
 
-// W_hh (4H x H) -> W_hh^T (H x 4H) so that the H > 64 forward reads it lane-contiguously
+// W_hh (4H x H) -> W_hh^T (H x 4H) so that the H > 64 forwards read it lane-contiguously (a grid-stride loop: at most 256
+// workgroups cover the 4 M elements of H = 1024)
 __global__ __launch_bounds__(256) void lstm_transpose_kernel(const LstmDesc* __restrict__ descs, Bases b) {
     const LstmDesc d = descs[blockIdx.y];        // by value: no descriptor re-reads after the per-step barriers
     if (d.H <= 64 || d.multi) return;
@@ -742,6 +911,7 @@ int launch_lstm_transpose(const LstmDesc* dev_descs, int count, int maxH, int mu
 }
 
 static int block_for(int maxH) {
+    if (lstm_band(maxH) == 2) return LSTM_WH;
     int t = (4 * maxH + 63) / 64 * 64;
     return t < 64 ? 64 : t;
 }
@@ -763,8 +933,10 @@ int launch_lstm_fwd(const LstmDesc* dev_descs, int count, int maxB, int maxH, in
         hipLaunchKernelGGL(lstm_fwd_group_kernel, dim3((maxB + LSTM_NS - 1) / LSTM_NS, count), dim3(256), 0, s, dev_descs, b);
     else if (maxH <= 64)
         hipLaunchKernelGGL((lstm_fwd_kernel<true>), dim3(maxB, count), dim3(block_for(maxH)), 0, s, dev_descs, b);
-    else
+    else if (lstm_band(maxH) == 1)
         hipLaunchKernelGGL((lstm_fwd_kernel<false>), dim3(maxB, count), dim3(block_for(maxH)), 0, s, dev_descs, b);
+    else
+        hipLaunchKernelGGL(lstm_fwd_wide_kernel, dim3(maxB, count), dim3(block_for(maxH)), 0, s, dev_descs, b);
     return (int)hipGetLastError();
 }
 
@@ -778,7 +950,9 @@ int launch_lstm_bwd(const LstmDesc* dev_descs, int count, int maxB, int maxH, in
         hipLaunchKernelGGL(lstm_bwd_group_kernel, dim3((maxB + LSTM_NS - 1) / LSTM_NS, count), dim3(256), 0, s, dev_descs, b);
     else if (maxH <= 64)
         hipLaunchKernelGGL((lstm_bwd_kernel<true>), dim3(maxB, count), dim3(block_for(maxH)), 0, s, dev_descs, b);
-    else
+    else if (lstm_band(maxH) == 1)
         hipLaunchKernelGGL((lstm_bwd_kernel<false>), dim3(maxB, count), dim3(block_for(maxH)), 0, s, dev_descs, b);
+    else
+        hipLaunchKernelGGL(lstm_bwd_wide_kernel, dim3(maxB, count), dim3(block_for(maxH)), 0, s, dev_descs, b);
     return (int)hipGetLastError();
 }

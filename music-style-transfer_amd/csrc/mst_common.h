@@ -172,6 +172,12 @@ struct LstmDesc {
 };
 #define LSTM_NB 12       // workgroups per sequence in the multi-workgroup flavour: 16 hidden units (64 gate rows) each at H = 192
 #define LSTM_MH 192
+#define LSTM_L2H 256     // largest H of the one-lane-per-gate-row L2 flavour
+#define LSTM_WH 1024     // largest H of the wide flavour = the largest LSTM hidden size a plan supports
+// single-workgroup flavour band of a hidden size: 0 registers (H <= 64), 1 L2 (<= LSTM_L2H), 2 wide (<= LSTM_WH); one launch
+// never mixes bands
+static inline int lstm_band(int H) { return H <= 64 ? 0 : (H <= LSTM_L2H ? 1 : 2); }
+static inline bool lstm_hidden_supported(int H) { return H >= 1 && H <= LSTM_WH; }
 
 // ---- combine (style/model.py:796-815): out = sum_c x_c n_c / sum_c n_c
 #define COMBINE_MAXC 32

@@ -163,6 +163,14 @@ static void build_params(const mst_dims& d, const Sizes& z, ParamTable& t) {
     t.lin(m + ".linear", NUF, NUF * 4);
 }
 
+// The one width rule of mst_widths_supported and plan construction: the note kernels' melody widths, and the hidden size of
+// each of the seven LSTMs (both channel encoders' beats / bars LSTMs, the style encoder's, the song-info beats / bars LSTMs)
+static bool widths_supported(const Sizes& z) {
+    for (const int h : {z.H, z.HB, z.SE_L, z.SIM_BL, z.NRF})
+        if (!lstm_hidden_supported(h)) return false;
+    return notes_widths_supported(z.MEL, z.ME_CW, z.PSA_ML);
+}
+
 static bool dims_ok(const mst_dims* d) {
     // C <= 24: the applier's backward kernel runs one wave per channel pair of a qf in ONE workgroup (LDS of 12 waves); a MIDI file
     // has 16 channels, so the reference's own inputs stop at 15 pitched channels
@@ -667,7 +675,7 @@ struct mst_plan {
         for (size_t i = 0; i < specs.size(); ++i) {
             const LstmSpec& sp = specs[i];
             const int H = sp.H;
-            if (4 * H > 1024) err = MST_ERR_UNSUPPORTED;
+            if (!lstm_hidden_supported(H)) err = MST_ERR_UNSUPPORTED;
             const std::string sfx = sp.reverse ? "_reverse" : "";
             const int64_t whh = pt.off(sp.pre + ".weight_hh_l0" + sfx), bhh = pt.off(sp.pre + ".bias_hh_l0" + sfx);
             const int64_t n = (int64_t)sp.B * sp.S;
@@ -695,7 +703,7 @@ struct mst_plan {
             maxTiles = std::max(maxTiles, ws.a);
             maxSplit = std::max(maxSplit, ws.b);
         }
-        if (maxH > 64 && minH <= 64) err = MST_ERR_UNSUPPORTED;       // one register/L2 flavour per launch
+        if (lstm_band(maxH) != lstm_band(minH)) err = MST_ERR_UNSUPPORTED;       // one register / L2 / wide flavour per launch
         const int cnt = (int)specs.size();
         if (maxH > 64) op.fwd.push_back(Step{K_LSTM_T, first, cnt, 0, maxH});
         op.fwd.push_back(Step{K_LSTM_F, first, cnt, maxB, maxH});
@@ -1154,8 +1162,7 @@ void mst_plan::build() {
         T v_rows{v.off, Q_ * NF * NUN, NUF * 4, NUF * 4};                  // x.view(..., n_unpitched_notes, -1)
         rowlin(AP, v_rows, true, m + ".linear", NUF, ACT_SIGOUT, "unpitched_pred");
     }
-    if (!notes_widths_supported(z.MEL, z.ME_CW, z.PSA_ML)) err = MST_ERR_UNSUPPORTED;
-    if (z.H > 256 || z.SE_L > 256 || z.HB > 256) err = MST_ERR_UNSUPPORTED;
+    if (!widths_supported(z)) err = MST_ERR_UNSUPPORTED;
 }
 
 // ------------------------------------------------------------------------------------------ scheduler
@@ -1426,8 +1433,8 @@ void mst_plan::schedule_pass(const std::vector<Step>& seq, std::vector<Step>& ou
                 if (done[j] || level[j] != lv) continue;
                 const Step& s = seq[j];
                 if (s.kind != s0.kind || (!across_stages && s.stage != s0.stage)) continue;
-                // LSTM launches come in a register-resident (H <= 64) and an L2 flavour
-                if (is_lstm && ((s.b > 64) != (s0.b > 64))) continue;
+                // LSTM launches come in a register-resident (H <= 64), an L2 (<= 256) and a wide (<= 1024) flavour
+                if (is_lstm && lstm_band(s.b) != lstm_band(s0.b)) continue;
                 // ... and the multi-workgroup flavour is a kernel of its own (grid and hidden size fixed): never merged with another
                 if (is_lstm && j != i && (lstms.host[s.first].multi || lstms.host[s0.first].multi)) continue;
                 if (j != i && !mergeable) continue;
@@ -1769,10 +1776,7 @@ int mst_plan::upload() {
 
 extern "C" int32_t mst_widths_supported(const mst_dims* d) {
     if (!dims_ok(d)) return MST_ERR_ARG;
-    const Sizes z = mst_sizes(*d);
-    if (!notes_widths_supported(z.MEL, z.ME_CW, z.PSA_ML)) return MST_ERR_UNSUPPORTED;
-    if (z.H > 256 || z.SE_L > 256 || z.HB > 256) return MST_ERR_UNSUPPORTED;
-    return MST_OK;
+    return widths_supported(mst_sizes(*d)) ? MST_OK : MST_ERR_UNSUPPORTED;
 }
 
 extern "C" mst_plan* mst_plan_create(const mst_dims* d, int32_t* status) { return mst_plan_create_ex(d, nullptr, status); }
