@@ -210,6 +210,13 @@ int32_t mst_hard_output(float* x, float* out, int64_t n_pos, int32_t nfeat, mst_
  * 29-31 lin.hip forward / input gradient / weight gradient. */
 int32_t mst_plan_step_count(const mst_plan* p, int32_t stage_mask, int32_t backward);
 int32_t mst_plan_step_info(const mst_plan* p, int32_t stage_mask, int32_t backward, int32_t* info /* 8 ints per step: 4 shape values, member count, kind, dependency level (inside its chain), chain (-1 = none) */);
+/* One int per step of the pass (the steps mst_plan_step_info lists): 0 = the step is launched on its own; 1 = the step, a gather
+ * or a segment reduce, has no launch of its own: it is carried by the GEMM step of its dependency level, whose gemm_kernel grid runs
+ * its workgroups in front of the GEMM members' (one-stream, merged plans on the 32x32 tiling only); 2 = a carried two-stage segment
+ * reduce: its first stage rides, its second stage stays a launch, directly behind the GEMM launch.  mst_plan_launch_count counts
+ * a carried step's first stage as 0 launches.  mst_plan_time_steps times the GEMM step together with everything it carries and
+ * reports a carried step as a row of 0 ms with its own FLOPs / bytes.  Returns the step count. */
+int32_t mst_plan_step_carried(const mst_plan* p, int32_t stage_mask, int32_t backward, int32_t* carried);
 /* (new) instrumentation: the members of GEMM launch step `step` of a pass, one clip's worth, 6 values each:
  * {M, N, K, k-splits, folded rows per clip (0 = not folded), workgroups}.  Returns the member count (<= cap). */
 int32_t mst_plan_step_gemms(const mst_plan* p, int32_t stage_mask, int32_t backward, int32_t step, int32_t* out, int32_t cap);

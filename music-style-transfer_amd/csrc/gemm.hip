@@ -720,18 +720,38 @@ int gemm_blocks(const GemmDesc& g, int mfma) {
     return ((ntile + run - 1) / run) * g.ksplit;
 }
 
+template <int WV> __device__ __forceinline__ void gather_rows(const GatherDesc& d, const int blk, const int nblk, const Bases& b);
+__device__ __forceinline__ void segred_group(const SegRedDesc* __restrict__ descs, const int members, const int clip, const int lb, const int t, const Bases& b);
+
 // One kernel for every GEMM of the model: blockIdx.y picks the descriptor, the descriptor's
 // (workgroup-uniform) variant picks the instantiation.  That lets the scheduler put *independent*
 // GEMMs of different kinds — e.g. the weight-gradient and input-gradient GEMMs of one layer, or
 // all small Linears of one dependency level — into a single launch.
-__global__ __launch_bounds__(GEMM_THREADS) void gemm_kernel(const GemmDesc* __restrict__ descs, const int* __restrict__ owner, int count, int blocks_per_clip, Bases b) {
+// The launch also carries its level's gathers and stage-1 segment reduces (GemmRiders): a clip's block range starts with the
+// segment-reduce blocks (the longest walk of the three, so dispatched first: four of segred_kernel's 256-lane groups each), then
+// the gather blocks (sixteen rows each, one per wave), then the GEMM members' tiles.  Rider blocks touch no LDS and meet no barrier.
+__global__ __launch_bounds__(GEMM_THREADS) void gemm_kernel(const GemmDesc* __restrict__ descs, const int* __restrict__ owner, int count, int blocks_per_clip, Bases b, GemmRiders r) {
     // A tile | B tile; the final reduce overlays the whole block with one 32x32 partial tile per wave
     constexpr int TILE_F = GEMM_BK * (GEMM_BM + GEMM_PAD), RED_F = (GEMM_THREADS / 64) * GEMM_BM * GEMM_BN;
     __shared__ float smem[(2 * TILE_F > RED_F) ? 2 * TILE_F : RED_F];
     float (*As)[GEMM_BM + GEMM_PAD] = reinterpret_cast<float (*)[GEMM_BM + GEMM_PAD]>(smem);
     float (*Bs)[GEMM_BN + GEMM_PAD] = reinterpret_cast<float (*)[GEMM_BN + GEMM_PAD]>(smem + TILE_F);
-    // flat 1-D grid: clip-major; inside a clip's block range member y owns [blk_begin, blk_begin + tiles * ksplit)
-    const int clip = blockIdx.x / blocks_per_clip, lb = blockIdx.x - clip * blocks_per_clip;
+    // flat 1-D grid: clip-major; inside a clip's block range, behind the riders, member y owns [blk_begin, blk_begin + tiles * ksplit)
+    const int clip = blockIdx.x / blocks_per_clip;
+    int lb = blockIdx.x - clip * blocks_per_clip;
+    const int seg_blocks = (r.seg_groups + 3) >> 2, gat_blocks = r.gat_members * r.gat_blocks;
+    if (lb < seg_blocks) {
+        const int grp = lb * 4 + (threadIdx.x >> 8);
+        if (grp < r.seg_groups) segred_group(r.segreds, r.seg_members, clip, grp, threadIdx.x & 255, b);
+        return;
+    }
+    lb -= seg_blocks;
+    if (lb < gat_blocks) {
+        const int m = lb / r.gat_blocks;
+        gather_rows<GATHER_RIDER_ROWS>(r.gathers[clip * r.gat_members + m], lb - m * r.gat_blocks, r.gat_blocks, b);
+        return;
+    }
+    lb -= gat_blocks;
     const int lo = owner[lb];                        // member of this block: one uniform load (the plan's block -> member table)
     const GemmDesc d = descs[clip * count + lo];     // by value (scalar loads once): a reference would be re-read after every barrier
     const int local = lb - d.blk_begin;
@@ -770,10 +790,15 @@ int gemm_variant(const GemmDesc& g) {
     return -1;
 }
 
-int launch_gemm(const GemmDesc* dev_descs, const int* dev_owner, int members, int blocks_per_clip, int clips, int mfma, Bases b, hipStream_t s) {
+int gemm_rider_blocks(const GemmRiders& r) { return (r.seg_groups + 3) / 4 + r.gat_members * r.gat_blocks; }
+
+int launch_gemm(const GemmDesc* dev_descs, const int* dev_owner, int members, int blocks_per_clip, int clips, int mfma, Bases b, hipStream_t s, const GemmRiders* riders) {
     if (members <= 0 || blocks_per_clip <= 0 || clips <= 0) return 0;
+    GemmRiders r = riders ? *riders : GemmRiders{};
+    if (mfma && gemm_rider_blocks(r)) return (int)hipErrorInvalidValue;        // only the 32x32 kernel carries riders
+    blocks_per_clip += gemm_rider_blocks(r);
     if (mfma) hipLaunchKernelGGL(gemm_mfma_kernel, dim3(blocks_per_clip * clips), dim3(MF_THREADS), 0, s, dev_descs, dev_owner, members, blocks_per_clip, b);
-    else hipLaunchKernelGGL(gemm_kernel, dim3(blocks_per_clip * clips), dim3(GEMM_THREADS), 0, s, dev_descs, dev_owner, members, blocks_per_clip, b);
+    else hipLaunchKernelGGL(gemm_kernel, dim3(blocks_per_clip * clips), dim3(GEMM_THREADS), 0, s, dev_descs, dev_owner, members, blocks_per_clip, b, r);
     return (int)hipGetLastError();
 }
 
@@ -783,10 +808,12 @@ int launch_gemm(const GemmDesc* dev_descs, const int* dev_owner, int members, in
 // dims the segment is broadcast over.  4 rows per workgroup (one wave each), lanes along the
 // concatenated feature axis (coalesced stores, broadcast/coalesced loads).  Its backward is the
 // segment reduce below applied to the gradient of the materialised tensor.
-__global__ __launch_bounds__(256) void gather_kernel(const GatherDesc* __restrict__ descs, Bases b) {
-    const GatherDesc& d = descs[blockIdx.y];       // no barriers here; dynamic seg[] indexing wants it in memory
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int row = blockIdx.x * 4 + wv; row < d.rows; row += gridDim.x * 4) {
+// `blk` of `nblk` blocks of WV rows each (one wave per row) walks member d's rows; whatever WV is, a row's elements are the same
+// loads added in the same (segment) order.
+template <int WV>
+__device__ __forceinline__ void gather_rows(const GatherDesc& d, const int blk, const int nblk, const Bases& b) {
+    const int lane = threadIdx.x & 63, wv = (threadIdx.x >> 6) & (WV - 1);
+    for (int row = blk * WV + wv; row < d.rows; row += nblk * WV) {
         unsigned t = (unsigned)row;
         int rc[4];
         rc[3] = t % (unsigned)d.d[3]; t /= (unsigned)d.d[3];
@@ -812,6 +839,10 @@ __global__ __launch_bounds__(256) void gather_kernel(const GatherDesc* __restric
             for (int w = lane; w < sg.width; w += 64) out[sg.start + w] = src[w];
         }
     }
+}
+
+__global__ __launch_bounds__(256) void gather_kernel(const GatherDesc* __restrict__ descs, Bases b) {
+    gather_rows<4>(descs[blockIdx.y], blockIdx.x, gridDim.x, b);       // no barriers here; dynamic seg[] indexing wants the descriptor in memory
 }
 
 int launch_gather(const GatherDesc* dev, int count, int max_rows, Bases b, hipStream_t s) {
@@ -858,9 +889,15 @@ __device__ __forceinline__ void segred_body(const SegRedDesc& d, const int item,
     const float* src = b.p[SP_GRAD] + d.src_off + d.start + w;
     const float* ysrc = b.p[SP_WS] + d.y_off + d.start + w;          // d.act: the activation whose derivative scales src
     const int64_t s3 = d.src_ld, s2 = s3 * d.d[3], s1 = s2 * d.d[2], s0 = s1 * d.d[1];
-    auto offset = [&]() { return (kc[0] + cr[0]) * s0 + (kc[1] + cr[1]) * s1 + (kc[2] + cr[2]) * s2 + (kc[3] + cr[3]) * s3; };
+    // the row's offset is carried along with the odometer: a step adds s3, a digit that wraps swaps its span for one step of the
+    // digit above (uniform constants) — recomputing it from the four digits cost four 64-bit multiplies per row and lane, and on a
+    // GEMM launch four waves share a SIMD's issue slots
+    const int64_t w3 = s2 - rd[3] * s3, w2 = s1 - rd[2] * s2, w1 = s0 - rd[1] * s1;
+    int64_t roff = (kc[0] + cr[0]) * s0 + (kc[1] + cr[1]) * s1 + (kc[2] + cr[2]) * s2 + (kc[3] + cr[3]) * s3;
+    auto offset = [&]() { return roff; };
     auto advance = [&]() {
-        if (++cr[3] == rd[3]) { cr[3] = 0; if (++cr[2] == rd[2]) { cr[2] = 0; if (++cr[1] == rd[1]) { cr[1] = 0; ++cr[0]; } } }
+        roff += s3;
+        if (++cr[3] == rd[3]) { cr[3] = 0; roff += w3; if (++cr[2] == rd[2]) { cr[2] = 0; roff += w2; if (++cr[1] == rd[1]) { cr[1] = 0; roff += w1; ++cr[0]; } } }
     };
     float acc[E];
 #pragma unroll
@@ -919,20 +956,26 @@ __device__ __forceinline__ void segred_body(const SegRedDesc& d, const int item,
     }
 }
 
-__global__ __launch_bounds__(256) void segred_kernel(const SegRedDesc* __restrict__ descs, int members, int blocks_per_clip, Bases b) {
-    // flat grid, clip-major: inside a clip's block range member y owns [blk_begin, blk_begin + ceil(nidx*nchunk*width / 256))
-    // (sized for one column per lane; a wide member uses the first quarter of its workgroups, the others retire at once)
-    const int clip = blockIdx.x / blocks_per_clip, lb = blockIdx.x - clip * blocks_per_clip;
+// Stage 1 for one group of 256 lanes: group `lb` of a clip's `members`-member block range (SegRedDesc.blk_begin counts such groups),
+// lane `t` of the group.
+__device__ __forceinline__ void segred_group(const SegRedDesc* __restrict__ descs, const int members, const int clip, const int lb, const int t, const Bases& b) {
     int y = 0;
     while (y + 1 < members && lb >= descs[y + 1].blk_begin) ++y;
     const SegRedDesc d = descs[clip * members + y];
-    const int e = (lb - d.blk_begin) * 256 + threadIdx.x;
+    const int e = (lb - d.blk_begin) * 256 + t;
     // four columns per lane only where nothing is reduced (a strided copy: index arithmetic per element was all its time, 68.7 ->
     // 40.6 us for the 456-wide one at 64 clips); a member that sums rows is latency bound and wants every lane it can get
     // (four columns per lane there: 33.6 -> 77.5 us)
     const bool copy = (d.kd[0] == 1 ? d.d[0] : 1) * (d.kd[1] == 1 ? d.d[1] : 1) * (d.kd[2] == 1 ? d.d[2] : 1) * (d.kd[3] == 1 ? d.d[3] : 1) == 1;
     if (copy && d.width >= 64) segred_body<4, 1>(d, e, b);
     else segred_body<1, 8>(d, e, b);
+}
+
+__global__ __launch_bounds__(256) void segred_kernel(const SegRedDesc* __restrict__ descs, int members, int blocks_per_clip, Bases b) {
+    // flat grid, clip-major: inside a clip's block range member y owns [blk_begin, blk_begin + ceil(nidx*nchunk*width / 256))
+    // (sized for one column per lane; a wide member uses the first quarter of its workgroups, the others retire at once)
+    const int clip = blockIdx.x / blocks_per_clip, lb = blockIdx.x - clip * blocks_per_clip;
+    segred_group(descs, members, clip, lb, threadIdx.x, b);
 }
 
 __global__ __launch_bounds__(256) void segred2_kernel(const SegRedDesc* __restrict__ descs, Bases b) {
@@ -949,12 +992,16 @@ __global__ __launch_bounds__(256) void segred2_kernel(const SegRedDesc* __restri
     }
 }
 
+int launch_segred2(const SegRedDesc* dev_descs, int count, int stage2_blocks, Bases b, hipStream_t s) {
+    if (count > 0 && stage2_blocks > 0) hipLaunchKernelGGL(segred2_kernel, dim3(stage2_blocks, count), dim3(256), 0, s, dev_descs, b);
+    return (int)hipGetLastError();
+}
+
 int launch_segred(const SegRedDesc* dev_descs, int members, int blocks_per_clip, int clips, int stage2_blocks, Bases b, hipStream_t s) {
     const int count = members * clips;
     if (count <= 0 || blocks_per_clip <= 0) return 0;
     hipLaunchKernelGGL(segred_kernel, dim3(blocks_per_clip * clips), dim3(256), 0, s, dev_descs, members, blocks_per_clip, b);
-    if (stage2_blocks > 0) hipLaunchKernelGGL(segred2_kernel, dim3(stage2_blocks, count), dim3(256), 0, s, dev_descs, b);
-    return (int)hipGetLastError();
+    return launch_segred2(dev_descs, count, stage2_blocks, b, s);
 }
 
 // ------------------------------------------------------------------------------------------

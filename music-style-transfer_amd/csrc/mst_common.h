@@ -153,6 +153,13 @@ struct SegRedDesc {
     int64_t y_off;
 };
 
+// ---- riders of a gemm_kernel launch: the gathers and stage-1 segment reduces of the GEMMs' dependency level, in the same grid.
+// Both tables are clips x members (clip-major), the ones a stand-alone gather_kernel / segred_kernel launch would be given.
+struct GemmRiders {
+    const SegRedDesc* segreds; int32_t seg_members, seg_groups;    // seg_groups: 256-lane groups per clip (segred_kernel's blocks_per_clip)
+    const GatherDesc* gathers; int32_t gat_members, gat_blocks;    // gat_blocks: workgroups of GATHER_RIDER_ROWS rows per member
+};
+
 // ---- LSTM recurrence
 struct LstmDesc {
     int32_t B, S, H, reverse;
@@ -340,10 +347,14 @@ int gemm_variant(const GemmDesc& g);
 // mfma = 1: the 64x64-tile f32-MFMA kernel (throughput), 0: the 32x32 split-K kernel (latency); blk_begin must have been
 // computed with the matching tile edge (gemm_tile_edge)
 // dev_owner: member index of every workgroup of one clip's block range (the plan's block -> member table of the launch)
-int launch_gemm(const GemmDesc* dev_descs, const int* dev_owner, int members, int blocks_per_clip, int clips, int mfma, Bases b, hipStream_t s);
+// riders (32x32 kernel only; nullptr = none): the launch's grid grows by gemm_rider_blocks() workgroups per clip in front of the members'
+int launch_gemm(const GemmDesc* dev_descs, const int* dev_owner, int members, int blocks_per_clip, int clips, int mfma, Bases b, hipStream_t s,
+                const GemmRiders* riders = nullptr);
+int gemm_rider_blocks(const GemmRiders& r);
 int gemm_tile_edge(int mfma);
 int gemm_blocks(const GemmDesc& g, int mfma);       // workgroups of one member (tiles / run x k-splits)
 int launch_segred(const SegRedDesc* dev_descs, int members, int blocks_per_clip, int clips, int stage2_blocks, Bases b, hipStream_t s);
+int launch_segred2(const SegRedDesc* dev_descs, int count, int stage2_blocks, Bases b, hipStream_t s);      // stage 2 alone (stage 1 rode on a GEMM launch)
 int launch_lstm_transpose(const LstmDesc* dev_descs, int count, int maxH, int multi, Bases b, hipStream_t s);
 int launch_lstm_fwd(const LstmDesc* dev_descs, int count, int maxB, int maxH, int multi, Bases b, hipStream_t s);
 int launch_lstm_bwd(const LstmDesc* dev_descs, int count, int maxB, int maxH, int multi, Bases b, hipStream_t s);
@@ -390,3 +401,4 @@ bool notes_widths_supported(int W, int CW, int ML);
 #define GEMM_BN 32
 #define GEMM_BK 128     // k-tile staged in LDS per step
 #define GEMM_THREADS 1024 // lanes per workgroup: 16 waves split every k-tile
+#define GATHER_RIDER_ROWS (GEMM_THREADS / 64)   // rows per gather rider workgroup of a gemm_kernel launch: one per wave

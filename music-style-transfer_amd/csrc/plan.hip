@@ -246,9 +246,15 @@ template <class D> struct DescTable {
     void release() { hipFree(dev); dev = nullptr; }
 };
 
-struct Step { int kind, first, count, a, b, stage; int c = 0; int lvl = 0; int chain = -1; int signal = -1; int wait[3] = {-1, -1, -1}; };
+// What a K_GEMM launch carries besides its members (mst_plan::mixes): its level's K_SEGRED step (first scheduled descriptor, members and
+// 256-lane groups per clip, stage-2 blocks) and K_GATHER step (first descriptor, members per clip, most rows of a member)
+struct Riders { int seg_first = 0, seg_members = 0, seg_groups = 0, seg_stage2 = 0, gat_first = 0, gat_members = 0, gat_rows = 0; };
+struct Step { int kind, first, count, a, b, stage; int c = 0; int lvl = 0; int chain = -1; int signal = -1; int wait[3] = {-1, -1, -1};
+              int carried = 0; Riders ride; };
 // c: GEMM steps — offset of the step's block -> member table; lvl: dependency level in its scheduled pass; chain / signal / wait: the stream the
 // launch goes to, the event slot recorded behind it and the slots its stream waits for in front of it (assign_streams; chain -1 = caller's stream)
+// carried: a gather / segment-reduce step that stays in the list (dependencies, first-writer flags, instrumentation) but is launched by
+// the K_GEMM step of its level, whose `ride` names its descriptors
 struct Acc { int space; int64_t lo, hi; bool w; bool accum = false, dense = true; };   // accum: a += writer; dense: covers [lo, hi) fully
 struct Op { int stage; std::vector<Step> fwd, bwd; };
 
@@ -285,6 +291,8 @@ struct mst_plan {
 
     // bar tiling (mst_plan_options.tile_rows > 0): this rank owns bars [tile_r0, tile_r0 + tile_rows) of the d.R bars
     bool tiled() const { return opt.tile_rows > 0; }
+    // a level's gathers and segment reduces ride on its GEMM launch: the one-stream, merged plans on the 32x32 tiling only
+    bool mixes() const { return !mfma && !tiled() && opt.branches != 1 && !opt.no_merge; }
     int Rl() const { return tiled() ? opt.tile_rows : d.R; }
     int P() const { return d.C * Rl() * d.T; }          // positions / beats this plan computes (all of them when not tiled)
     int Q() const { return Rl() * d.T; }
@@ -1422,6 +1430,7 @@ void mst_plan::schedule_pass(const std::vector<Step>& seq, std::vector<Step>& ou
     }
     std::vector<char> done(n, 0);
     for (int lv = 0; lv <= maxlevel; ++lv) {
+        const size_t lv_begin = out.size();
         for (int i = 0; i < n; ++i) {
             if (done[i] || level[i] != lv) continue;
             const Step& s0 = seq[i];
@@ -1503,6 +1512,22 @@ void mst_plan::schedule_pass(const std::vector<Step>& seq, std::vector<Step>& ou
                 m.a = total;
             }
             out.push_back(m);
+        }
+        // Steps of one level are independent, so the level's gather and segment-reduce launches (stage 1) ride on its GEMM launch
+        // (of the same stage where stages may run separately).  The carried steps stay in the list; run_step skips them.
+        if (!mixes()) continue;
+        for (size_t e = lv_begin; e < out.size(); ++e) {
+            if (out[e].kind != K_GATHER && out[e].kind != K_SEGRED) continue;
+            for (size_t c = lv_begin; c < out.size(); ++c) {
+                Step& g = out[c];
+                if (g.kind != K_GEMM || (!across_stages && g.stage != out[e].stage)) continue;
+                const Step& s = out[e];
+                if (s.kind == K_GATHER && !g.ride.gat_members) { g.ride.gat_first = s.first; g.ride.gat_members = s.count / K(); g.ride.gat_rows = s.a; }
+                else if (s.kind == K_SEGRED && !g.ride.seg_members) { g.ride.seg_first = s.first; g.ride.seg_members = s.count / K(); g.ride.seg_groups = s.a; g.ride.seg_stage2 = s.b; }
+                else continue;
+                out[e].carried = 1;
+                break;
+            }
         }
     }
 }
@@ -1844,7 +1869,8 @@ extern "C" int32_t mst_plan_launch_count(const mst_plan* p, int32_t mask, int32_
     int n = 0;
     for (auto& s : p->list(mask, backward)) {
         if (!(s.stage & mask)) continue;
-        n += (((s.kind == K_COMB_F || s.kind == K_COMB_B) && s.b != 0) || (s.kind == K_SEGRED && s.b > 0)) ? 2 : 1;
+        const int stage2 = (((s.kind == K_COMB_F || s.kind == K_COMB_B) && s.b != 0) || (s.kind == K_SEGRED && s.b > 0)) ? 1 : 0;
+        n += (s.carried ? 0 : 1) + stage2;          // a carried step's first stage is part of its level's GEMM launch
     }
     if (backward) for (int s = 0; s < 3; ++s) if ((mask >> s) & 1) n += 1;
     return n;
@@ -1861,8 +1887,15 @@ static Bases make_bases(const mst_plan* p, const float* params, float* gparams, 
 }
 
 static int run_step(const mst_plan* p, const Step& s, const Bases& b, hipStream_t st) {
+    if (s.carried) return 0;              // launched by the K_GEMM step of its level
     switch (s.kind) {
-    case K_GEMM: case K_GEMM_FOLD: return launch_gemm(p->gemms.dev + s.first, p->d_gemm_owner + s.c, s.b, s.a, s.count / s.b, p->mfma, b, st);
+    case K_GEMM: case K_GEMM_FOLD: {
+        const Riders& q = s.ride;
+        const int clips = s.count / s.b, gat_blocks = std::min(512, (q.gat_rows + GATHER_RIDER_ROWS - 1) / GATHER_RIDER_ROWS);
+        const GemmRiders r{p->segreds.dev + q.seg_first, q.seg_members, q.seg_groups, p->gathers.dev + q.gat_first, q.gat_members, gat_blocks};
+        const int e = launch_gemm(p->gemms.dev + s.first, p->d_gemm_owner + s.c, s.b, s.a, clips, p->mfma, b, st, &r);
+        return e ? e : launch_segred2(p->segreds.dev + q.seg_first, q.seg_members * clips, q.seg_stage2, b, st);
+    }
     case K_GATHER: return launch_gather(p->gathers.dev + s.first, s.count, s.a, b, st);
     case K_SEGRED: return launch_segred(p->segreds.dev + s.first, s.count / p->K(), s.a, p->K(), s.b, b, st);
     case K_LSTM_T: return launch_lstm_transpose(p->lstms.dev + s.first, s.count, s.b, p->lstms.sched[s.first].multi, b, st);
@@ -2191,6 +2224,13 @@ extern "C" int64_t mst_plan_zero_floats(const mst_plan* p, int32_t mask) {
     return n;
 }
 
+extern "C" int32_t mst_plan_step_carried(const mst_plan* p, int32_t mask, int32_t backward, int32_t* carried) {
+    if (!p || !carried) return MST_ERR_ARG;
+    int n = 0;
+    for (auto& s : p->list(mask, backward)) if (s.stage & mask) carried[n++] = !s.carried ? 0 : ((s.kind == K_SEGRED && s.b > 0) ? 2 : 1);
+    return n;
+}
+
 extern "C" int32_t mst_plan_step_count(const mst_plan* p, int32_t mask, int32_t backward) {
     if (!p) return MST_ERR_ARG;
     int n = 0;
@@ -2251,6 +2291,12 @@ extern "C" int32_t mst_plan_time_steps(const mst_plan* p, int32_t mask, int32_t 
     for (auto& s : p->list(mask, backward)) if (s.stage & mask) steps.push_back(&s);
     int idx = 0;
     for (const Step* s : steps) {
+        if (s->carried) {                             // timed inside its level's GEMM step: 0 ms here, with its own work
+            ms[idx] = 0.f; kind[idx] = s->kind;
+            step_cost(p, *s, &flops[idx], &bytes[idx]);
+            ++idx;
+            continue;
+        }
         run_step(p, *s, b, st);                       // warm
         hipEventRecord(e0, st);
         for (int r = 0; r < reps; ++r) run_step(p, *s, b, st);

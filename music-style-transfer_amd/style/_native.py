@@ -107,6 +107,7 @@ _SIGS = {
     'mst_hard_output': (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P]),
     'mst_plan_step_count': (C.c_int32, [_P, C.c_int32, C.c_int32]),
     'mst_plan_step_info': (C.c_int32, [_P, C.c_int32, C.c_int32, _P]),
+    'mst_plan_step_carried': (C.c_int32, [_P, C.c_int32, C.c_int32, _P]),
     'mst_plan_step_gemms': (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32]),
     'mst_plan_time_steps': (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P]),
     'mst_audio_plan_create': (_P, [C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32)]),
@@ -313,6 +314,16 @@ class Plan:
         if got != n:
             check(got if got < 0 else -1, 'mst_plan_time_steps')
         return list(zip(kind.tolist(), ms.tolist(), fl.tolist(), by.tolist()))
+
+    def step_carried(self, mask=STAGE_ALL, backward=False):
+        """One int per step of the pass: 0 = launched on its own, 1 = a gather / segment reduce that its level's GEMM launch
+        carries, 2 = carried, with a second stage that is still a launch of its own."""
+        import numpy as np
+        n = self.lib.mst_plan_step_count(self.handle, mask, int(backward))
+        out = np.zeros(n, np.int32)
+        got = self.lib.mst_plan_step_carried(self.handle, mask, int(backward), out.ctypes.data)
+        check(got if got < 0 else 0, 'mst_plan_step_carried')
+        return out.tolist()
 
     def step_gemms(self, mask, backward, step, cap=2048):
         """[(M, N, K, k_splits, fold_rows, workgroups)] of the members (one clip's worth) of GEMM launch step `step`."""

@@ -42,5 +42,8 @@ for bwd in (False, True):
     print('==== backward' if bwd else '==== forward')
     for i, ((kind, ms, fl, by), inf) in enumerate(zip(steps, info)):
         tot += ms
+        if ms == 0:          # a gather / segment reduce carried by its level's GEMM launch: timed inside that row
+            print(f'{i:3d} {KIND_NAMES[kind]:22s}  carried    {fl/1e6:9.2f} MFLOP {by/1e6:8.2f} MB  (in the gemm_kernel row of level {inf[6]})  info={inf.tolist()}')
+            continue
         print(f'{i:3d} {KIND_NAMES[kind]:22s} {ms*1e3:8.1f} us  {fl/1e6:9.2f} MFLOP {by/1e6:8.2f} MB  {fl/ms/1e9:7.2f} TF {by/ms/1e6:7.1f} GB/s  info={inf.tolist()}')
 print('sum of steps: %.3f ms' % tot)
