@@ -66,7 +66,7 @@ int32_t mst_param_info(const mst_dims* d, int32_t i, char* name, int32_t name_ca
                        int64_t* offset, int32_t* ndim, int32_t shape[3]);
 
 /* MST_OK when the HIP kernels are instantiated for the layer widths in `d` (the note-level kernels exist for
- * melody_size 8 and 4 with the reference's derived widths; the hidden size of each of the seven LSTMs is at most 1024),
+ * melody_size 4, 8, 12 and 16 — a multiple of 4 from 4 to 16 — with the reference's derived widths; the hidden size of each of the seven LSTMs is at most 1024),
  * MST_ERR_UNSUPPORTED otherwise.  mst_plan_create applies the same rule, so the Python constructors fail early
  * instead of at the first forward. */
 int32_t mst_widths_supported(const mst_dims* d);

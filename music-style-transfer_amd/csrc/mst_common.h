@@ -34,6 +34,15 @@
 // that also stores, that wait (vmcnt counts stores too on gfx9) would drain the previous iteration's stores every iteration
 #define MST_PIN(x) asm volatile("" : "+v"(x))
 #endif
+// makes a wave-uniform pointer opaque HERE (it stays in its SGPR pair; no instruction is emitted): loads through it cannot be
+// hoisted above this point.  Device code only; on the host and in the interpreter it is nothing.
+#ifndef MST_PIN_SGPR
+#if defined(__AMDGCN__)
+#define MST_PIN_SGPR(p) asm volatile("" : "+s"(p))
+#else
+#define MST_PIN_SGPR(p) ((void)(p))
+#endif
+#endif
 #ifndef MST_LDS_BARRIER
 #define MST_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 #endif

@@ -64,6 +64,15 @@ struct MeWeights {
     cptr wc, bc, wl, bl;
     __device__ __forceinline__ MeWeights(const NotesDesc& d, const float* par)
         : wc((cptr)(par + d.wc_off)), bc((cptr)(par + d.bc_off)), wl((cptr)(par + d.wl_off)), bl((cptr)(par + d.bl_off)) {}
+    // A copy whose pointers the compiler cannot trace back (W > 8 only; the copy IS the original up to W = 8).  The scalar loads
+    // of a loop body that reads the weights through it stay inside the loop: hoisted out of the position / fraction loops, the
+    // 318 (W = 12) or 514 (W = 16) weights of me_notes_bwd were kept in SGPRs spilled to VGPR lanes and from there to scratch
+    // (566 SGPR spills and 708 bytes of scratch per lane at W = 16).
+    __device__ __forceinline__ MeWeights here() const {
+        MeWeights r = *this;
+        if constexpr (W > 8) { MST_PIN_SGPR(r.wc); MST_PIN_SGPR(r.bc); MST_PIN_SGPR(r.wl); MST_PIN_SGPR(r.bl); }
+        return r;
+    }
 };
 
 // One note of one channel: cat (W + CW) and x_c (W).  The octave / degree half of cat — and with it the first W terms of the
@@ -230,11 +239,14 @@ __global__ __launch_bounds__(256, ME_FWD_MINW) void me_notes_fwd_kernel(const No
 // One wave per (position, half of the fractions): the two waves of a position are neighbours in one workgroup and meet
 // once, at the end of the position, to add their octave / degree partial sums (fixed order: half 0 + half 1).
 template <int W, int CW>
-__global__ __launch_bounds__(256, ME_BWD_MINW) void me_notes_bwd_kernel(const NotesDesc* __restrict__ dp, Bases b) {
+__global__ __launch_bounds__(256, W <= 8 ? ME_BWD_MINW : 2) void me_notes_bwd_kernel(const NotesDesc* __restrict__ dp, Bases b) {
     const NotesDesc d = dp[blockIdx.y];
     constexpr int KL = W + CW;
     constexpr int R_WC = 0, R_BC = CW * NPF, R_WL = R_BC + CW, R_BL = R_WL + W * KL;
-    static_assert(KL + 1 <= 16 && W <= 16 && CW <= 16, "one 16x16 MFMA tile per product");
+    // gm^T [cat | 1] has KL + 1 columns: one 16-column MFMA tile up to W = 8, two (NT) at W = 12 / 16; the other two products
+    // (CW x 6 and 15 x W) keep one tile
+    constexpr int NT = (KL + 1 + 15) / 16;
+    static_assert(NT <= 2 && W <= 16 && CW <= 16 && NPF + 1 <= 16, "rows of every product in one 16-row MFMA tile");
     // transposed staging rows of one wave: gm (W) | cat (KL) | gc (CW) | x (5) | god (W)
     constexpr int T_GM = 0, T_CAT = W, T_GC = W + KL, T_X = T_GC + CW, T_GOD = T_X + NPF, T_ROWS = T_GOD + W;
     const MeWeights<W, CW> wt(d, b.p[SP_PAR]);
@@ -261,6 +273,7 @@ __global__ __launch_bounds__(256, ME_BWD_MINW) void me_notes_bwd_kernel(const No
     const float S = tmp[d.stats_off + d.C];
     const float bsum = wave_sum64(lane < d.nwc ? tmp[d.part_off + (int64_t)d.C * d.nwc + lane] : 0.f);
     nt_f32x4 accW = {0.f, 0.f, 0.f, 0.f}, accC = {0.f, 0.f, 0.f, 0.f};
+    nt_f32x4 accW1 = {0.f, 0.f, 0.f, 0.f};                 // columns 16 .. KL of gm^T [cat | 1] (NT == 2)
     const int P = d.C * d.Q;
     constexpr int F0 = NF / 2;
     const int f_begin = fh * F0, f_end = fh ? NF : F0;
@@ -281,7 +294,7 @@ __global__ __launch_bounds__(256, ME_BWD_MINW) void me_notes_bwd_kernel(const No
             float octv[W], degv[W], cat_od[W], pre[W], gmsum[W];
             ld_vec<W>(ws + d.oct_off + ((int64_t)p * NOCT + o) * W, octv);
             ld_vec<W>(ws + d.deg_off + ((int64_t)p * NDEG + dg) * W, degv);
-            me_pos<W, CW>(wt, octv, degv, cat_od, pre);
+            me_pos<W, CW>(wt.here(), octv, degv, cat_od, pre);
 #pragma unroll
             for (int j = 0; j < W; ++j) gmsum[j] = 0.f;
             // ---- per fraction: the note-feature half.  dW_linear[:, W:] | db_linear = gm^T [catx | 1],  dW_channels | db = gc^T [x | 1]
@@ -289,7 +302,8 @@ __global__ __launch_bounds__(256, ME_BWD_MINW) void me_notes_bwd_kernel(const No
                 float x5[NPF], catx[CW], out[W], gv[W];
                 ld_x5(x, ((int64_t)p * NF + f) * NPN + n, x5);
                 ld_vec<W>(gr + d.g_out_off + (((int64_t)q * NF + f) * NPN + n) * W, gv);
-                me_frac<W, CW>(wt, pre, x5, catx, out);
+                const MeWeights<W, CW> wf = wt.here();
+                me_frac<W, CW>(wf, pre, x5, catx, out);
                 float gm[W];
 #pragma unroll
                 for (int j = 0; j < W; ++j) {              // combine backward, then the linear's leaky
@@ -304,7 +318,7 @@ __global__ __launch_bounds__(256, ME_BWD_MINW) void me_notes_bwd_kernel(const No
                 for (int k = 0; k < CW; ++k) {
                     float gsum = 0.f;
 #pragma unroll
-                    for (int j = 0; j < W; ++j) gsum = fmaf(gm[j], wt.wl[j * KL + W + k], gsum);
+                    for (int j = 0; j < W; ++j) gsum = fmaf(gm[j], wf.wl[j * KL + W + k], gsum);
                     t[T_CAT + W + k][lane] = catx[k];
                     t[T_GC + k][lane] = gsum * dlrelu(catx[k]);
                 }
@@ -316,8 +330,15 @@ __global__ __launch_bounds__(256, ME_BWD_MINW) void me_notes_bwd_kernel(const No
                     const int k = 4 * s + kh;
                     const float a1 = r < W ? t[T_GM + (r < W ? r : 0)][k] : 0.f;
                     // columns 0 .. W-1 (the octave / degree half of cat) are added once per position, below
-                    const float b1 = (r >= W && r < KL) ? t[T_CAT + ((r >= W && r < KL) ? r : W)][k] : (r == KL ? 1.f : 0.f);
-                    accW = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, accW, 0, 0, 0);
+                    // (W = 16: column tile 0 holds nothing but that half)
+                    if constexpr (W < 16) {
+                        const float b1 = (r >= W && r < KL) ? t[T_CAT + ((r >= W && r < KL) ? r : W)][k] : (r == KL ? 1.f : 0.f);
+                        accW = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, accW, 0, 0, 0);
+                    }
+                    if constexpr (NT == 2) {
+                        const float b1 = 16 + r < KL ? t[T_CAT + (16 + r < KL ? 16 + r : W)][k] : (16 + r == KL ? 1.f : 0.f);
+                        accW1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, accW1, 0, 0, 0);
+                    }
                     const float a2 = r < CW ? t[T_GC + (r < CW ? r : 0)][k] : 0.f;
                     const float b2 = r < NPF ? t[T_X + (r < NPF ? r : 0)][k] : (r == NPF ? 1.f : 0.f);
                     accC = __builtin_amdgcn_mfma_f32_16x16x4f32(a2, b2, accC, 0, 0, 0);
@@ -329,11 +350,12 @@ __global__ __launch_bounds__(256, ME_BWD_MINW) void me_notes_bwd_kernel(const No
             MST_WAVE_SYNC();
 #pragma unroll
             for (int j = 0; j < W; ++j) t[T_GM + j][lane] = gmsum[j];
+            const MeWeights<W, CW> wp = wt.here();
 #pragma unroll
             for (int i = 0; i < W; ++i) {
                 float gsum = 0.f;
 #pragma unroll
-                for (int j = 0; j < W; ++j) gsum = fmaf(gmsum[j], wt.wl[j * KL + i], gsum);
+                for (int j = 0; j < W; ++j) gsum = fmaf(gmsum[j], wp.wl[j * KL + i], gsum);
                 t[T_CAT + i][lane] = cat_od[i];
                 t[T_GOD + i][lane] = gsum * dlrelu(cat_od[i]);
             }
@@ -343,7 +365,7 @@ __global__ __launch_bounds__(256, ME_BWD_MINW) void me_notes_bwd_kernel(const No
                 const int k = 4 * s + kh;
                 const float a1 = r < W ? t[T_GM + (r < W ? r : 0)][k] : 0.f;
                 const float b1 = r < W ? t[T_CAT + (r < W ? r : 0)][k] : 0.f;
-                accW = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, accW, 0, 0, 0);
+                accW = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, accW, 0, 0, 0);      // W <= 16: column tile 0
                 const float b3 = r < W ? t[T_GOD + (r < W ? r : 0)][k] : 0.f;
                 accO = __builtin_amdgcn_mfma_f32_16x16x4f32((float)((ohmask >> s) & 1u), b3, accO, 0, 0, 0);
                 if ((s & 3) == 3) MST_SCHED_FENCE();
@@ -369,7 +391,7 @@ __global__ __launch_bounds__(256, ME_BWD_MINW) void me_notes_bwd_kernel(const No
     // one slab row per workgroup: channels_linear.{weight,bias}, linear.{weight,bias} in parameter order; the four waves'
     // partial sums meet in wave order
     constexpr int NWT = R_BL + W;
-    static_assert(NWT <= 256, "slab row wider than the workgroup");
+    static_assert(4 * NWT <= 4 * T_ROWS * NT_ROW, "slab rows wider than the staging they reuse");
     float* wsum = &tr[0][0][0];                            // the staging rows are free now: 4 x NWT floats
     __syncthreads();
 #pragma unroll
@@ -377,14 +399,22 @@ __global__ __launch_bounds__(256, ME_BWD_MINW) void me_notes_bwd_kernel(const No
         const int row = 4 * kh + rr;
         if (row < W) {
             if (r < KL) wsum[wv * NWT + R_WL + row * KL + r] = accW[rr]; else if (r == KL) wsum[wv * NWT + R_BL + row] = accW[rr];
+            if constexpr (NT == 2) {
+                if (16 + r < KL) wsum[wv * NWT + R_WL + row * KL + 16 + r] = accW1[rr]; else if (16 + r == KL) wsum[wv * NWT + R_BL + row] = accW1[rr];
+            }
         }
         if (row < CW) {
             if (r < NPF) wsum[wv * NWT + R_WC + row * NPF + r] = accC[rr]; else if (r == NPF) wsum[wv * NWT + R_BC + row] = accC[rr];
         }
     }
     __syncthreads();
-    if (tid < NWT)
-        b.p[SP_TMP][d.slab_off + (int64_t)blockIdx.x * d.slab_stride + tid] = (wsum[tid] + wsum[NWT + tid]) + (wsum[2 * NWT + tid] + wsum[3 * NWT + tid]);
+    if constexpr (NWT <= 256) {
+        if (tid < NWT)
+            b.p[SP_TMP][d.slab_off + (int64_t)blockIdx.x * d.slab_stride + tid] = (wsum[tid] + wsum[NWT + tid]) + (wsum[2 * NWT + tid] + wsum[3 * NWT + tid]);
+    } else {                                               // a row wider than the workgroup (318 floats at W = 12, 514 at W = 16): in strides
+        for (int w = tid; w < NWT; w += 256)
+            b.p[SP_TMP][d.slab_off + (int64_t)blockIdx.x * d.slab_stride + w] = (wsum[w] + wsum[NWT + w]) + (wsum[2 * NWT + w] + wsum[3 * NWT + w]);
+    }
 }
 
 // ============================================================================ PitchedStyleApplier
@@ -588,7 +618,7 @@ __global__ __launch_bounds__(64 * NPB, PSA_BWD_MINW) void psa_bwd2_kernel(const 
     const gptr_t y0 = (gptr_t)(ws + d.out_off), t0 = (gptr_t)tgt;
     const gptr_t rto0 = (gptr_t)(ws + d.rt_oct_off), rtd0 = (gptr_t)(ws + d.rt_deg_off), mel0 = (gptr_t)(ws + d.mel_off);
     typedef float mel_f4 __attribute__((ext_vector_type(4)));
-    static_assert(MEL % 4 == 0 && NPN * MEL / 4 <= 64 * NPB * 2, "melody rows staged with at most two 16-byte loads per lane");
+    static_assert(MEL % 4 == 0, "melody rows staged with 16-byte loads");
     struct QfIn { float rt[NOD], y[NSLOT], t[NSLOT]; };
     // flat element e = lane + 64 q of the pair's (row A | row B): q < 4 lies in row A, q > 4 in row B, q = 4 straddles
     const unsigned rowA = (unsigned)((2 * wv < d.C ? 2 * wv : 0) * QF) * ROWE + lane;
@@ -731,8 +761,11 @@ __global__ __launch_bounds__(64 * NPB, PSA_BWD_MINW) void psa_bwd2_kernel(const 
         }
         __syncthreads();
         // ---- the melody-linear columns from the channel sums, and melody_linear's own backward
+        // (W > 8: a real loop — unrolled over its up to 28 notes per lane with 2 x MEL weight / gradient registers live, the
+        // one- and two-wave buckets spilled 12 to 248 bytes per lane)
+        constexpr int MEL_UNROLL = MEL > 8 ? 1 : MAXN;
         if (mact) {
-#pragma unroll
+#pragma unroll MEL_UNROLL
             for (int u = 0; u < MAXN; ++u) {
                 const int n = G + u * NGT;
                 if (n < NPN) {
@@ -847,24 +880,31 @@ __global__ __launch_bounds__(64 * NPB, PSA_BWD_MINW) void psa_bwd2_kernel(const 
 }
 
 // ============================================================================ dispatch
+// The one melody-width rule: rows of `melody` and of the octave / degree tensors are read with 16-byte loads (a multiple of
+// 4), and the note kernels are instantiated for W = 4, 8, 12, 16 with the widths the model derives from W (mst_sizes):
+// CW = ceil((5 + W) / 2) = 5, 7, 9, 11 and ML = ceil(3 (W + 5) / 2) = 14, 20, 26, 32.
 bool notes_widths_supported(int W, int CW, int ML) {
-    bool me = (W == 8 && CW == 7) || (W == 4 && CW == 5);
-    bool psa = ML == 20 || ML == 14;
-    return me && psa;
+    return W >= 4 && W <= 16 && W % 4 == 0 && CW == (NPF + W + 1) / 2 && ML == (3 * (W + NPF) + 1) / 2;
 }
 
 #define ME_DISPATCH(KERN, GRID, BLOCK)                                                              \
     if (h.W == 8 && h.CW == 7) hipLaunchKernelGGL((KERN<8, 7>), GRID, BLOCK, 0, s, dev, b);           \
     else if (h.W == 4 && h.CW == 5) hipLaunchKernelGGL((KERN<4, 5>), GRID, BLOCK, 0, s, dev, b);      \
+    else if (h.W == 12 && h.CW == 9) hipLaunchKernelGGL((KERN<12, 9>), GRID, BLOCK, 0, s, dev, b);    \
+    else if (h.W == 16 && h.CW == 11) hipLaunchKernelGGL((KERN<16, 11>), GRID, BLOCK, 0, s, dev, b);  \
     else return MST_ERR_UNSUPPORTED;
 #define PSA_DISPATCH(KERN, GRID, BLOCK)                                                             \
     if (h.ML == 20 && h.W == 8) hipLaunchKernelGGL((KERN<20, 8>), GRID, BLOCK, 0, s, dev, b);         \
     else if (h.ML == 14 && h.W == 4) hipLaunchKernelGGL((KERN<14, 4>), GRID, BLOCK, 0, s, dev, b);    \
+    else if (h.ML == 26 && h.W == 12) hipLaunchKernelGGL((KERN<26, 12>), GRID, BLOCK, 0, s, dev, b);  \
+    else if (h.ML == 32 && h.W == 16) hipLaunchKernelGGL((KERN<32, 16>), GRID, BLOCK, 0, s, dev, b);  \
     else return MST_ERR_UNSUPPORTED;
 
 #define ME_RED_DISPATCH(BWD, GRID, BLOCK)                                                              \
     if (h.W == 8 && h.CW == 7) hipLaunchKernelGGL((me_reduce_kernel<8, 7, BWD>), GRID, BLOCK, 0, s, dev, b);     \
     else if (h.W == 4 && h.CW == 5) hipLaunchKernelGGL((me_reduce_kernel<4, 5, BWD>), GRID, BLOCK, 0, s, dev, b); \
+    else if (h.W == 12 && h.CW == 9) hipLaunchKernelGGL((me_reduce_kernel<12, 9, BWD>), GRID, BLOCK, 0, s, dev, b);   \
+    else if (h.W == 16 && h.CW == 11) hipLaunchKernelGGL((me_reduce_kernel<16, 11, BWD>), GRID, BLOCK, 0, s, dev, b); \
     else return MST_ERR_UNSUPPORTED;
 int launch_me_sumsq(const NotesDesc* dev, const NotesDesc& h, int count, Bases b, hipStream_t s) {
     ME_RED_DISPATCH(false, dim3((h.C * h.nwc + 3) / 4, count), dim3(256));
@@ -902,6 +942,8 @@ int launch_psa_notes_bwd(const NotesDesc* dev, const NotesDesc& h, int count, Ba
     const dim3 grid(h.nblk, count);
     if (h.ML == 20 && h.W == 8) { PSA_BWD_BUCKETS(20, 8) }
     else if (h.ML == 14 && h.W == 4) { PSA_BWD_BUCKETS(14, 4) }
+    else if (h.ML == 26 && h.W == 12) { PSA_BWD_BUCKETS(26, 12) }
+    else if (h.ML == 32 && h.W == 16) { PSA_BWD_BUCKETS(32, 16) }
     else return MST_ERR_UNSUPPORTED;
     return (int)hipGetLastError();
 }

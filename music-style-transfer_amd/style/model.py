@@ -259,10 +259,10 @@ class StyleTransferModel(nn.Module):
                     raise ValueError(f'sub-modules disagree on {k}_size: {widths[k]} vs {v}')
         self._widths = widths
         self._link_children()
-        # fail here, not at the first forward: the note-level HIP kernels exist for melody_size 8 and 4 only
+        # fail here, not at the first forward: the note-level HIP kernels exist for melody_size 4, 8, 12 and 16 only
         if _native.get().lib.mst_widths_supported(_dims(**widths)) != 0:
             raise _native.MstError(f'layer widths {widths} are outside the instantiated HIP kernels '
-                                   '(melody_size must be 8 or 4; LSTM hidden sizes <= 1024)')
+                                   '(melody_size must be a multiple of 4 from 4 to 16; LSTM hidden sizes <= 1024)')
         self._flat = self._gflat = None
         self._offsets = self._ends = self._slots = None
         self.graph_repeated_shapes = True       # train_iteration(): replay a hipGraph when a clip shape comes back
