@@ -203,6 +203,20 @@ int32_t mst_adam_step2(float* params, float* grads, float* grads2, float* exp_av
  * Like the reference it also zeroes sub-threshold velocities of `x` in place. */
 int32_t mst_hard_output(float* x, float* out, int64_t n_pos, int32_t nfeat, mst_stream stream);
 
+/* ---- sparse clip input: build dense note tensors from sorted note records on the device.
+ * A piano roll is > 98 % zeros, so a clip travels as records and is expanded here.  For each clip k of n_clips:
+ *   cells[k * capacity + i]            flat cell index (C order of the roll without its feature axis), strictly ascending in i
+ *   feats[(k * capacity + i) * nfeat]  the cell's nfeat (5 pitched / 2 unpitched) floats
+ *   counts[k]                          live records of clip k, read ON THE DEVICE (a captured graph replays with another clip);
+ *                                      clamped to [0, capacity]; records beyond it are ignored
+ * out: n_clips x n_cells x nfeat floats.  EVERY float is written — the record's value or +0.0 — so the caller never clears the
+ * buffer and stale (or NaN) contents of a reused one disappear.  A record whose cell is outside [0, n_cells) is skipped, never
+ * stored.  One launch, enqueue-only on `stream` (no allocation, no host synchronisation, capturable), no atomics: bit-reproducible.
+ * out needs float alignment only.  MST_ERR_ARG: null pointer, nfeat outside {2, 5}, n_cells < 1 or >= 2^31, n_clips < 1,
+ * capacity < 0. */
+int32_t mst_clip_scatter(const int32_t* cells, const float* feats, const int32_t* counts, int32_t capacity, int32_t n_clips,
+                         int64_t n_cells, int32_t nfeat, float* out, mst_stream stream);
+
 /* ---- instrumentation (bench.py only; synchronises on HIP events, never used for training):
  * average duration of every launch step of a pass, with its algorithmic FLOPs and bytes.
  * kind: 0 gemm, 1 gather, 2 segment-reduce, 3/4 lstm fwd/bwd, 5/6 combine fwd/bwd, 7/8 melody notes, 9/10 applier notes,

@@ -526,3 +526,110 @@ extern "C" int32_t mst_hard_output(float* x, float* out, int64_t n_pos, int32_t 
     hipLaunchKernelGGL(hard_output_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, x, out, n_pos, (int)nfeat);
     return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
 }
+
+// ------------------------------------------------------------------ sparse clip input (mst_clip_scatter)
+// A clip arrives as sorted (cell, features) records; the dense note tensor the kernels read is built here.  The destination is cut
+// into 16-byte-aligned slices of SCAT_SLICE floats, one workgroup each: the workgroup zero-fills an LDS image of its slice, drops the
+// records that fall into the slice into the image and streams the image out with 16-byte stores.  Every float of the destination is
+// written exactly once, by the one workgroup that owns it: no atomics, no clearing pass, stale or NaN contents never read.
+#define SCAT_SLICE 2048          // floats per workgroup: 8 KB of LDS, two 16-byte stores per lane
+#define SCAT_THREADS 256
+
+// Lower bounds of two targets in the ascending cells[0, n), found by the whole workgroup: per round every lane samples the last cell
+// of its 1/256 share of the remaining range, so two dependent loads settle up to 64 k records (a per-lane binary search is a chain
+// of ~13).  Both searches share the barriers.  On cells that are not ascending the result is some index in [0, n]: the caller
+// bounds-checks every record it stores.
+__device__ __forceinline__ void scatter_bounds(const int32_t* cells, int n, int t0, int t1, int* flag, int* sel, int& lb0, int& lb1) {
+    const int tid = threadIdx.x;
+    int64_t a[2] = {0, 0}, b[2] = {n, n};
+    const int tg[2] = {t0, t1};
+    while (b[0] > a[0] || b[1] > a[1]) {           // workgroup-uniform
+        int64_t s[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int64_t len = b[j] - a[j];
+            s[j] = (len + SCAT_THREADS - 1) / SCAT_THREADS;
+            const int64_t idx = a[j] + (int64_t)tid * s[j] + s[j] - 1;
+            flag[j * SCAT_THREADS + tid] = (len > 0 && idx < b[j] && cells[idx] < tg[j]) ? 1 : 0;
+        }
+        if (tid < 2) sel[tid] = 0;
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 2; ++j)                // the last lane whose sample is still below the target
+            if (flag[j * SCAT_THREADS + tid] && (tid == SCAT_THREADS - 1 || !flag[j * SCAT_THREADS + tid + 1])) sel[j] = tid + 1;
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            if (b[j] > a[j]) {
+                const int64_t na = a[j] + (int64_t)sel[j] * s[j], nb = na + s[j] - 1;
+                a[j] = na < b[j] ? na : b[j];
+                b[j] = nb < b[j] ? nb : b[j];
+            }
+        }
+        __syncthreads();                           // flag / sel are rewritten by the next round
+    }
+    lb0 = (int)a[0];
+    lb1 = (int)a[1];
+}
+
+// grid = slices of the shifted flat destination: g = flat index + shift, shift = floats between the previous 16-byte boundary and
+// out, so that g = 0 (mod 4) is a 16-byte-aligned address whatever the alignment of out
+template <int NFEAT>
+__global__ __launch_bounds__(SCAT_THREADS) void clip_scatter_kernel(const int32_t* cells, const float* feats, const int32_t* counts,
+                                                                    int capacity, int64_t n_cells, int64_t total, float* out, int shift) {
+    __shared__ float4 img4[SCAT_SLICE / 4];
+    __shared__ int flag[2 * SCAT_THREADS], sel[2];
+    float* img = reinterpret_cast<float*>(img4);
+    const int tid = threadIdx.x;
+    const int64_t gb = (int64_t)blockIdx.x * SCAT_SLICE;
+    const int64_t g0 = gb > shift ? gb : shift;
+    const int64_t g1 = gb + SCAT_SLICE < shift + total ? gb + SCAT_SLICE : shift + total;
+    for (int i = tid; i < SCAT_SLICE / 4; i += SCAT_THREADS) img4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    __syncthreads();
+    const int64_t per = n_cells * NFEAT, f0 = g0 - shift, f1 = g1 - shift;
+    for (int64_t k = f0 / per; k * per < f1; ++k) {                  // the clips this slice touches (one, or two at a seam)
+        const int64_t lo = f0 > k * per ? f0 - k * per : 0;          // clip-local floats [lo, hi) of this slice
+        const int64_t hi = f1 - k * per < per ? f1 - k * per : per;
+        int n = counts[k];
+        n = n < 0 ? 0 : (n > capacity ? capacity : n);               // whatever lies beyond the count is ignored
+        const int32_t* ck = cells + k * capacity;
+        const float* fk = feats + k * (int64_t)capacity * NFEAT;
+        int r0, r1;                                                   // records of the cells that overlap [lo, hi)
+        scatter_bounds(ck, n, (int)(lo / NFEAT), (int)((hi + NFEAT - 1) / NFEAT), flag, sel, r0, r1);
+        for (int64_t e = tid; e < (int64_t)(r1 - r0) * NFEAT; e += SCAT_THREADS) {
+            const int64_t r = r0 + e / NFEAT;
+            const int64_t local = (int64_t)ck[r] * NFEAT + e % NFEAT;
+            // a cell that straddles the slice edge is shared float by float; a cell >= n_cells has local >= per >= hi
+            if (local >= lo && local < hi) img[k * per + local + shift - gb] = fk[r * NFEAT + e % NFEAT];
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < SCAT_SLICE / 4; i += SCAT_THREADS) {
+        const int64_t g = gb + 4 * i;
+        if (g >= g0 && g + 4 <= g1) {
+            *reinterpret_cast<float4*>(out + (g - shift)) = img4[i];
+        } else {                                                      // the ragged head and tail of the destination
+            for (int j = 0; j < 4; ++j)
+                if (g + j >= g0 && g + j < g1) out[g + j - shift] = img[4 * i + j];
+        }
+    }
+}
+
+extern "C" int32_t mst_clip_scatter(const int32_t* cells, const float* feats, const int32_t* counts, int32_t capacity,
+                                    int32_t n_clips, int64_t n_cells, int32_t nfeat, float* out, mst_stream stream) {
+    if (!cells || !feats || !counts || !out || capacity < 0 || n_clips < 1 || n_cells < 1 || n_cells >= ((int64_t)1 << 31) ||
+        (nfeat != 5 && nfeat != 2) || ((uintptr_t)out & 3))
+        return MST_ERR_ARG;
+    const int shift = (int)(((uintptr_t)out & 15) / 4);
+    const int64_t total = (int64_t)n_clips * n_cells * nfeat;
+    const int64_t nb = (shift + total + SCAT_SLICE - 1) / SCAT_SLICE;
+    if (nb > 0x7fffffff) return MST_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    if (nfeat == 5)
+        hipLaunchKernelGGL(clip_scatter_kernel<5>, dim3((unsigned)nb), dim3(SCAT_THREADS), 0, s, cells, feats, counts, (int)capacity,
+                           n_cells, total, out, shift);
+    else
+        hipLaunchKernelGGL(clip_scatter_kernel<2>, dim3((unsigned)nb), dim3(SCAT_THREADS), 0, s, cells, feats, counts, (int)capacity,
+                           n_cells, total, out, shift);
+    return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
+}

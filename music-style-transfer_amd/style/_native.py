@@ -105,6 +105,7 @@ _SIGS = {
     'mst_adam_step2': (C.c_int32, [_P, _P, _P, _P, _P, C.c_int64, _P, C.c_double, C.c_double, C.c_double, C.c_double,
                                    C.c_int32, C.c_double, C.c_int32, _P]),
     'mst_hard_output': (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P]),
+    'mst_clip_scatter': (C.c_int32, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _P, _P]),
     'mst_plan_step_count': (C.c_int32, [_P, C.c_int32, C.c_int32]),
     'mst_plan_step_info': (C.c_int32, [_P, C.c_int32, C.c_int32, _P]),
     'mst_plan_step_carried': (C.c_int32, [_P, C.c_int32, C.c_int32, _P]),
@@ -167,6 +168,16 @@ class Native:
 
     def param_floats(self, dims):
         return self.lib.mst_param_floats(C.byref(dims))
+
+    def clip_scatter(self, cells, feats, counts, out, n_cells, nfeat, n_clips=1, capacity=None, stream=None):
+        """mst_clip_scatter: dense `out` (n_clips x n_cells x nfeat floats) from sorted note records.  `cells` (int32), `feats`
+        (float32), `counts` (int32) are tensors on out's device or raw addresses; `capacity` = records per clip in the buffers
+        (default: cells.numel() // n_clips).  Enqueue-only."""
+        if capacity is None:
+            capacity = cells.numel() // n_clips
+        addr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()
+        check(self.lib.mst_clip_scatter(addr(cells), addr(feats), addr(counts), int(capacity), int(n_clips), int(n_cells), int(nfeat),
+                                        addr(out), stream), 'mst_clip_scatter')
 
     def plan(self, dims, device):
         opts = options_from_env()

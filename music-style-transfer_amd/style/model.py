@@ -21,6 +21,7 @@ import torch
 from torch import nn
 
 from style import _native
+from style.sparse import SparseRoll, scatter_packed
 from style.utils.pytorch import Distributed, LSTM
 
 epsilon = 1e-7
@@ -350,7 +351,12 @@ class StyleTransferModel(nn.Module):
 
     # ---- reference surface (style/model.py:751-793) ----------------------------------------
     # Grad mode is read HERE: inside autograd.Function.forward it is always off, so the Functions take it as a plain bool.
+    def _dense(self, roll):
+        """A note tensor given as a SparseRoll, densified on the model's device by mst_clip_scatter; anything else as it is."""
+        return roll.to_dense(self._anchor().device) if isinstance(roll, SparseRoll) else roll
+
     def extract_style(self, mode, bpm, pitched_channels, instruments_features, unpitched_channels=None):
+        pitched_channels, unpitched_channels = self._dense(pitched_channels), self._dense(unpitched_channels)
         return _Extract.apply(self, self._anchor(), torch.is_grad_enabled(), mode, bpm, pitched_channels, instruments_features,
                               unpitched_channels)
 
@@ -375,8 +381,12 @@ class StyleTransferModel(nn.Module):
         in-place accumulation gives).  p.grad shows lane 0's share until then."""
         anchor = self._anchor()
         dev = anchor.device
-        pitched = _f32c(pitched_channels, dev)
-        unpitched = None if unpitched_channels is None else _f32c(unpitched_channels, dev)
+        # a note tensor may come as a SparseRoll (style.data): its records are uploaded on the lane's stream and
+        # mst_clip_scatter writes the lane's static buffer directly, in place of the device-to-device copy of a dense tensor
+        note = lambda t: t if t is None or isinstance(t, SparseRoll) else _f32c(t, dev)
+        pitched, unpitched = note(pitched_channels), note(unpitched_channels)
+        sparse = [t for t in (pitched, unpitched) if isinstance(t, SparseRoll)]
+        new_buf = lambda t: None if t is None else torch.empty(tuple(t.shape), dtype=torch.float32, device=dev)
         _, C, R, T = pitched.shape[:4]
         plan = self._plan(C, R, T, unpitched is not None, dev)
         lanes = self._lanes(dev)
@@ -389,7 +399,7 @@ class StyleTransferModel(nn.Module):
         st = plan.__dict__.setdefault('_lane_state', {}).get(li)
         if st is None:
             st = plan._lane_state[li] = dict(ws=plan.ws if li == 0 else plan.new_ws(), graph=None, key=None, uses=0,
-                                             pitched=torch.empty_like(pitched), unpitched=None if unpitched is None else torch.empty_like(unpitched),
+                                             pitched=new_buf(pitched), unpitched=new_buf(unpitched), records={},
                                              losses=torch.empty(_native.N_LOSSES, dtype=torch.float32, device=dev))
         ws = st['ws']
         small = [_f32c(mode, dev).reshape(-1), _f32c(bpm, dev).reshape(-1), _f32c(instruments_features, dev).reshape(-1),
@@ -400,17 +410,19 @@ class StyleTransferModel(nn.Module):
         side = lane['stream'] if li or getattr(self, 'concurrent_accumulation', False) else cur
         if side is not cur:
             side.wait_stream(cur)                      # the caller's inputs (and the last optimizer step) are ready
-            for t in small + [pitched] + ([unpitched] if unpitched is not None else []):
+            for t in small + [t for t in (pitched, unpitched) if torch.is_tensor(t)]:
                 t.record_stream(side)
         with torch.cuda.stream(side):
             # the note tensors are copied into the lane's static buffers unless the caller already wrote them there
             # (static_inputs()): a captured graph reads fixed addresses
             srcs, dsts = list(small), list(slots)
-            if pitched.data_ptr() != st['pitched'].data_ptr():
+            if torch.is_tensor(pitched) and pitched.data_ptr() != st['pitched'].data_ptr():
                 srcs.append(pitched.reshape(-1)); dsts.append(st['pitched'].reshape(-1))
-            if unpitched is not None and unpitched.data_ptr() != st['unpitched'].data_ptr():
+            if torch.is_tensor(unpitched) and unpitched.data_ptr() != st['unpitched'].data_ptr():
                 srcs.append(unpitched.reshape(-1)); dsts.append(st['unpitched'].reshape(-1))
             torch._foreach_copy_(dsts, srcs)           # one launch for all of them
+            for roll in sparse:
+                _scatter_records(roll, st['pitched'] if roll is pitched else st['unpitched'], st['records'], dev)
             # A shape seen before replays a hipGraph of the whole loop body (the launches of mst_train_iteration captured once
             # per plan and lane over static input buffers); songs of a new shape run eagerly.  Keyed by the buffers it baked in.
             key = (self._flat.data_ptr(), gflat.data_ptr())
@@ -495,9 +507,44 @@ class StyleTransferModel(nn.Module):
                     cur.wait_stream(lane['stream'])
 
     def forward(self, mode, bpm, pitched_channels, instruments_features, unpitched_channels=None):
+        pitched_channels, unpitched_channels = self._dense(pitched_channels), self._dense(unpitched_channels)
         ip, mp, bp, xp, xu = _Forward.apply(self, self._anchor(), torch.is_grad_enabled(), mode, bpm, pitched_channels,
                                             instruments_features, unpitched_channels)
         return (ip, mp, bp), xp, (xu if unpitched_channels is not None else None)
+
+
+def _scatter_records(roll, out, holder, dev):
+    """Upload a SparseRoll's records and expand them into `out` (a lane's static note buffer), all enqueued on the current
+    stream.  `holder` keeps, per feature count, the lane's device record buffer — grown by doubling, never per call — and the
+    pinned staging slots for rolls whose records are not in pinned memory already."""
+    if out is None or out.numel() != roll.n_cells * roll.nfeat:
+        raise _native.MstError(f'{roll!r} does not have the shape of the note tensor it stands for')
+    words = roll.packed.numel()
+    slot = holder.setdefault(roll.nfeat, dict(dev=None, stage=[], at=0))
+    if slot['dev'] is None or slot['dev'].numel() < words:
+        grown = max(words, 2 * slot['dev'].numel() if slot['dev'] is not None else 1 << 12)
+        slot['dev'] = torch.empty(grown, dtype=torch.int32, device=dev)       # (the old one is recycled in stream order)
+    src = roll.packed
+    if not src.is_pinned():
+        # two staging slots, each reused only after the copy that last read it has completed: its event is waited for
+        # (long over in the steady state: two calls of this lane have gone by)
+        if not slot['stage']:
+            slot['stage'] = [dict(buf=None, done=None) for _ in range(2)]
+        stage = slot['stage'][slot['at'] % 2]
+        slot['at'] += 1
+        if stage['done'] is not None and not stage['done'].query():
+            stage['done'].synchronize()
+        if stage['buf'] is None or stage['buf'].numel() < words:
+            stage['buf'] = torch.empty(max(words, 2 * stage['buf'].numel() if stage['buf'] is not None else 1 << 12),
+                                       dtype=torch.int32, pin_memory=True)
+        stage['buf'][:words].copy_(src)
+        src = stage['buf'][:words]
+        slot['dev'][:words].copy_(src, non_blocking=True)
+        stage['done'] = stage['done'] or torch.cuda.Event()
+        stage['done'].record()
+    else:
+        slot['dev'][:words].copy_(src, non_blocking=True)   # (the host allocator keeps a pinned block until this copy is over)
+    scatter_packed(_native.get(), slot['dev'], roll.count, roll.n_cells, roll.nfeat, out, _native.current_stream(dev))
 
 
 def _shapes(model, C, R, T):

@@ -1,0 +1,107 @@
+"""Piano rolls as sorted note records (`style.data.SparseRoll`, re-exported there).
+
+A roll is > 98 % zeros: a song holds 400 to 6100 non-zero cells in 2 to 37 MB of float32.  A SparseRoll keeps, per non-zero
+cell, its flat index (C order of the roll without the feature axis) and its 5 / 2 features.  The host keeps them in ONE int32
+buffer — header, cells, feature bits — so a clip goes to the device as one copy of a few hundred KB at most, and
+mst_clip_scatter builds the dense tensor the kernels read there.  `densify(sparsify(x))` is `x.astype(float32)` bit for bit.
+
+No reference counterpart: the reference uploads dense rolls (style/data.py:130-156).
+"""
+import numpy as np
+import torch
+
+from style import _native
+
+HEADER = 4            # int32 words in front of the cells: [count, 0, 0, 0] (keeps the cells 16-byte aligned)
+
+
+def _cells_words(count):
+    """Words the cells take in the packed buffer: padded to a multiple of 4 (so the features stay 16-byte aligned), never 0."""
+    return max(4, (count + 3) & ~3)
+
+
+def packed_words(count, nfeat):
+    return HEADER + _cells_words(count) + count * nfeat
+
+
+class SparseRoll:
+    """Note records of one dense roll of `shape` (feature axis last): `cells` int32 (n,), strictly ascending; `feats` float32
+    (n, nfeat).  Both are views of `packed`, the int32 buffer that is uploaded; `pin=True` puts it in pinned host memory
+    (default: when a GPU is present)."""
+
+    def __init__(self, cells, feats, shape, pin=None):
+        shape = tuple(int(d) for d in shape)
+        if len(shape) < 2 or shape[-1] not in (2, 5):
+            raise ValueError(f'shape {shape}: the last axis holds the 5 pitched or 2 unpitched note features')
+        nfeat = shape[-1]
+        n_cells = int(np.prod(shape[:-1], dtype=np.int64))
+        if not 1 <= n_cells < 2 ** 31:
+            raise ValueError(f'shape {shape}: {n_cells} cells, need 1 <= cells < 2**31')
+        cells = np.ascontiguousarray(torch.as_tensor(cells).numpy() if torch.is_tensor(cells) else cells)
+        feats = np.ascontiguousarray(torch.as_tensor(feats).numpy() if torch.is_tensor(feats) else feats)
+        if cells.ndim != 1 or cells.dtype.kind not in 'iu':
+            raise ValueError('cells: a 1-d integer array')
+        n = cells.shape[0]
+        feats = feats.reshape(n, nfeat) if feats.size == n * nfeat else feats
+        if feats.shape != (n, nfeat):
+            raise ValueError(f'feats: shape {feats.shape}, expected {(n, nfeat)}')
+        if n:
+            c64 = cells.astype(np.int64)
+            if c64.min() < 0 or c64.max() >= n_cells:
+                raise ValueError(f'cells out of range [0, {n_cells})')
+            if np.any(np.diff(c64) <= 0):
+                raise ValueError('cells must be strictly ascending (sorted, no duplicates)')
+        if pin is None:
+            pin = torch.cuda.is_available()
+        self.shape, self.nfeat, self.n_cells, self.count = shape, nfeat, n_cells, n
+        self.packed = torch.zeros(packed_words(n, nfeat), dtype=torch.int32, pin_memory=bool(pin))
+        self.packed[0] = n
+        at = HEADER + _cells_words(n)
+        self.cells = self.packed[HEADER:HEADER + n]
+        self.feats = self.packed[at:at + n * nfeat].view(torch.float32).view(n, nfeat)
+        self.cells.numpy()[:] = cells
+        self.feats.numpy()[:] = feats.astype(np.float32, copy=False)
+
+    def __repr__(self):
+        return f'SparseRoll(shape={self.shape}, records={self.count})'
+
+    def any(self):
+        """np.any of the dense roll, from the records."""
+        return bool(np.any(self.feats.numpy()))
+
+    def to_numpy(self):
+        """The dense float32 roll, built on the host."""
+        out = np.zeros((self.n_cells, self.nfeat), dtype=np.float32)
+        out[self.cells.numpy()] = self.feats.numpy()
+        return out.reshape(self.shape)
+
+    def to_dense(self, device, out=None, native=None):
+        """The dense float32 roll on `device`, built there by mst_clip_scatter on the current stream (the records are uploaded
+        asynchronously when they are pinned).  `out`: a contiguous float32 tensor of the roll's size to write into — every float
+        of it is overwritten.  `native`: another build of the C ABI (tests: the CPU interpreter build)."""
+        device = torch.device(device)
+        if out is None:
+            out = torch.empty(self.shape, dtype=torch.float32, device=device)
+        elif out.numel() != self.n_cells * self.nfeat or out.dtype != torch.float32 or not out.is_contiguous():
+            raise _native.MstError('to_dense(out=): a contiguous float32 tensor with the roll\'s number of elements')
+        records = self.packed.to(device, non_blocking=True) if device.type == 'cuda' else self.packed
+        scatter_packed(native or _native.get(), records, self.count, self.n_cells, self.nfeat, out, _native.current_stream(device))
+        return out
+
+
+def scatter_packed(native, records, count, n_cells, nfeat, out, stream):
+    """Enqueue mst_clip_scatter over a packed record buffer (SparseRoll.packed, or its copy on out's device)."""
+    base = records.data_ptr()
+    cells = base + 4 * HEADER
+    native.clip_scatter(cells, cells + 4 * _cells_words(count), base, out, n_cells, nfeat, n_clips=1, capacity=count, stream=stream)
+
+
+def sparsify(roll, pin=None):
+    """Dense roll (any float dtype, feature axis last) -> SparseRoll.  The roll is converted to float32 FIRST; a cell is kept
+    when the float32 bit pattern of any of its features is not all-zero (so -0.0 survives): densifying gives back
+    `roll.astype(float32)` bit for bit."""
+    x = roll.detach().cpu().numpy() if torch.is_tensor(roll) else np.asarray(roll)
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    bits = x.view(np.uint32).reshape(-1, x.shape[-1])
+    cells = np.flatnonzero(bits.any(axis=1))
+    return SparseRoll(cells.astype(np.int32), x.reshape(bits.shape)[cells], x.shape, pin=pin)

@@ -21,13 +21,13 @@ import torch
 
 from style import _native
 from style.data import (iter_inputs, instrument_size, n_instruments, included_instruments, prepare_input,
-                        get_used_instruments)
+                        prepare_input_sparse, get_used_instruments)
 from style.model import (device, get_total_loss, PitchedChannelsEncoder, UnpitchedChannelsEncoder, PitchedRhythmEncoder,
                          UnpitchedRhythmEncoder, StyleEncoder, MelodyEncoder, SongInfoModel, PitchedStyleApplier,
                          UnpitchedStyleApplier, StyleTransferModel)
 from style.optim import FusedAdam
 from style.utils.misc import ProgressBar, assert_dir
-from style.utils.parallel import iter_parallel
+from style.utils.parallel import iter_parallel, ParallelIterable
 
 CSV_FIELDS = ['iteration'] + _native.LOSS_KEYS
 
@@ -57,6 +57,43 @@ def drop_silent(input):
     if unpitched is not None and not np.any(unpitched[:, :max_n_bars]):
         unpitched = None
     return (filename, (info, pitched, features, instruments, unpitched)), max_n_bars
+
+
+def iter_sparse(inputs):
+    """The sparse input path's share of the host pipeline, meant for the prefetch thread: every song of `inputs` cut to the
+    `800 // C` bars the model will see and turned into note records (style.data.SparseClip) with silence dropped on the
+    records as `drop_silent` drops it on the rolls; None stands for a song without pitched notes."""
+    for input in inputs:
+        max_n_bars = 800 // input[1][1].shape[0]
+        # pageable memory: this runs beside the loop thread, which captures hipGraphs, and allocating pinned memory is not
+        # allowed while a stream captures; train_iteration stages the records through its own pinned slots
+        yield prepare_input_sparse(input, max_n_bars, pin=False).drop_silent()
+
+
+class SmallInputStager:
+    """The small host inputs of an iteration (mode, bpm, instrument features, used instruments) as ONE asynchronous upload
+    through a ring of reusable pinned buffers, so that the loop thread allocates no pinned memory per iteration.  A buffer is
+    reused only after the event behind its last copy (long over by then: `slots` iterations have gone by)."""
+
+    def __init__(self, device, slots=4):
+        self.device, self.at = device, 0
+        self.slots = [dict(buf=None, done=None) for _ in range(slots)]
+
+    def upload(self, *tensors):
+        """Device copies of the float32 host tensors (views of one device buffer, on the current stream)."""
+        flat = [torch.as_tensor(t, dtype=torch.float32).reshape(-1) for t in tensors]
+        n = sum(t.numel() for t in flat)
+        slot = self.slots[self.at % len(self.slots)]
+        self.at += 1
+        if slot['done'] is not None and not slot['done'].query():
+            slot['done'].synchronize()
+        if slot['buf'] is None or slot['buf'].numel() < n:
+            slot['buf'] = torch.empty(max(n, 1 << 12), dtype=torch.float32, pin_memory=True)
+        torch.cat(flat, out=slot['buf'][:n])
+        dev = slot['buf'][:n].to(self.device, non_blocking=True)
+        slot['done'] = slot['done'] or torch.cuda.Event()
+        slot['done'].record()
+        return tuple(part.view(t.shape) for part, t in zip(dev.split([t.numel() for t in flat]), tensors))
 
 
 class LossLog:
@@ -111,23 +148,54 @@ class LossLog:
 
 
 def train(model, inputs, n_iterations=5000, iter_size=2, training_info_path='training.csv', save_path='snapshots/',
-          save_interval=100, flush_every=20, progress=True, optimizer=None, fused=True):
+          save_interval=100, flush_every=20, progress=True, optimizer=None, fused=True, sparse_input=False):
     """`inputs`: iterator of (filename, get_input(...)) tuples, e.g. iter_parallel(iter_inputs(...)).
     fused=True runs a loop body as ONE C-ABI call (StyleTransferModel.train_iteration: same arithmetic, same gradients, no
-    autograd graph); fused=False is the reference's own sequence model(...) -> get_total_loss -> backward."""
+    autograd graph); fused=False is the reference's own sequence model(...) -> get_total_loss -> backward.
+    sparse_input=True feeds the note tensors as sorted note records: a prefetch thread cuts and sparsifies the songs
+    (iter_sparse), this loop only enqueues the upload of the records (a few hundred KB at most, through pinned memory) and the
+    kernel that builds the dense tensors on the device (mst_clip_scatter).  Same tensors bit for bit, hence the same losses.
+    The prefetch thread runs ahead of the loop: when train() returns it has taken one or two songs more from `inputs` than
+    the loop used, and it is told to stop and joined for up to 5 s — a daemon thread that is still blocked inside the
+    caller's iterator after that (a slow parse) ends with it."""
+    feeder = None
+    if sparse_input:
+        feeder = ParallelIterable(iter_sparse(inputs))
+        inputs = iter(feeder)
+    try:
+        return _train_loop(model, inputs, n_iterations, iter_size, training_info_path, save_path, save_interval, flush_every,
+                           progress, optimizer, fused, sparse_input)
+    finally:
+        if feeder is not None:
+            feeder.stop(timeout=5.)
+
+
+def _train_loop(model, inputs, n_iterations, iter_size, training_info_path, save_path, save_interval, flush_every, progress,
+                optimizer, fused, sparse_input):
     optimizer = optimizer or FusedAdam(model, lr=.01, step_size=200, gamma=.9)
     optimizer.zero_grad()
     pbar = ProgressBar(n_iterations) if progress else None
     log = LossLog(training_info_path, pbar, flush_every, health=getattr(model, 'check_device_status', None))
+    stager = SmallInputStager(device) if sparse_input else None
     for iteration in range(n_iterations):
-        input, max_n_bars = drop_silent(next(inputs))
+        if sparse_input:
+            input = next(inputs)
+        else:
+            input, max_n_bars = drop_silent(next(inputs))
         if input is None:
             if pbar is not None:
                 pbar.n_iterations -= 1
             continue
-        info = input[1][0]
-        mode, bpm, pitched, features, unpitched = prepare_input(input, max_n_bars)
-        used = get_used_instruments(features, unpitched)
+        if sparse_input:
+            info = dict(bpm=input.bpm_target)
+            mode, bpm, pitched, features, unpitched = input
+            mode, bpm, features, used = stager.upload(mode, bpm, features, get_used_instruments(features, unpitched))
+            if not fused:                          # the autograd path's loss reads the dense targets
+                pitched, unpitched = model._dense(pitched), model._dense(unpitched)
+        else:
+            info = input[1][0]
+            mode, bpm, pitched, features, unpitched = prepare_input(input, max_n_bars)
+            used = get_used_instruments(features, unpitched)
         if fused:
             packed = model.train_iteration(mode, bpm, pitched, features, unpitched, used, info['bpm'])
         else:
