@@ -217,6 +217,28 @@ int32_t mst_hard_output(float* x, float* out, int64_t n_pos, int32_t nfeat, mst_
 int32_t mst_clip_scatter(const int32_t* cells, const float* feats, const int32_t* counts, int32_t capacity, int32_t n_clips,
                          int64_t n_cells, int32_t nfeat, float* out, mst_stream stream);
 
+/* ---- sparse clip output: the sorted note records of a dense roll, built on the device — the inverse of mst_clip_scatter, so
+ * that inference downloads the notes (24 bytes per pitched record) instead of the whole roll.  x: n_cells x nfeat floats.
+ *   MST_ROLL_NONZERO  a cell is a record when the float32 BIT PATTERN of any of its features is non-zero (-0.0 and NaN are
+ *                     kept); features verbatim.  The inverse of mst_clip_scatter.
+ *   MST_ROLL_HARD     hard_output's decisions (style/model.py:818-832), in mst_hard_output's order: feature 0 the duration,
+ *                     feature 1 v > .01f ? v : 0, for nfeat == 5 features 2-4 (x[a] == max && x[a] > .1f) ? 1 : 0.  A cell is a
+ *                     record when its hard velocity is non-zero (v > .01f; a NaN velocity is dropped); the record carries the
+ *                     HARD features.  Unlike mst_hard_output, x is not modified.
+ * The roll is cut into mst_roll_slices(n_cells) slices of consecutive cells.  mst_roll_count leaves in ws (mst_roll_slices + 1
+ * int32) the number of records in the slices before slice s at ws[s], and the total at ws[slices].  mst_roll_compact, given
+ * that ws, writes the record of rank r < capacity to cells[r] (flat cell index, strictly ascending in r) and
+ * feats[r * nfeat ...]; records of rank >= capacity are dropped, never stored: nothing outside cells[0, min(total, capacity))
+ * and the matching floats is written.  Two launches and one; enqueue-only on `stream` (no allocation, no host synchronisation,
+ * capturable); no atomics, no workgroup waits for another: the output is bit-identical run to run.  x needs float alignment
+ * only.  MST_ERR_ARG: null pointer, n_cells < 1 or >= 2^31, nfeat outside {2, 5}, mode outside {0, 1}, capacity < 0, x not
+ * 4-byte aligned. */
+enum { MST_ROLL_NONZERO = 0, MST_ROLL_HARD = 1 };
+int64_t mst_roll_slices(int64_t n_cells);      /* slices the kernels cut n_cells into; <= 0 on a bad argument */
+int32_t mst_roll_count(const float* x, int64_t n_cells, int32_t nfeat, int32_t mode, int32_t* ws, mst_stream stream);
+int32_t mst_roll_compact(const float* x, int64_t n_cells, int32_t nfeat, int32_t mode, const int32_t* ws,
+                         int64_t capacity, int32_t* cells, float* feats, mst_stream stream);
+
 /* ---- instrumentation (bench.py only; synchronises on HIP events, never used for training):
  * average duration of every launch step of a pass, with its algorithmic FLOPs and bytes.
  * kind: 0 gemm, 1 gather, 2 segment-reduce, 3/4 lstm fwd/bwd, 5/6 combine fwd/bwd, 7/8 melody notes, 9/10 applier notes,

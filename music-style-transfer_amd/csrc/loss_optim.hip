@@ -633,3 +633,221 @@ extern "C" int32_t mst_clip_scatter(const int32_t* cells, const float* feats, co
                            n_cells, total, out, shift);
     return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
 }
+
+// ------------------------------------------------------------------ sparse clip output (mst_roll_count, mst_roll_compact)
+// The inverse of the scatter: the sorted (cell, features) records of a dense roll, so that only the notes go back to the host.
+// An ordered stream compaction in the usual three steps — per-slice counts, an exclusive scan of the counts, emit — with no atomics
+// and no workgroup waiting for another: the records, and their order, are the same bits on every run.  One workgroup owns a slice
+// of ROLL_SLICE consecutive cells.  A cell is 20 or 8 bytes, so a lane loading "its" cell would issue unaligned strided loads:
+// the workgroup stages the slice into LDS with 16-byte loads instead and evaluates the predicate from the image.  The emit pass
+// reads the slice a second time and recomputes the predicate (no per-cell mask is kept), packs the records in LDS in cell order
+// and streams them out contiguously.
+#define ROLL_SLICE 1024          // cells per workgroup: 20 KB of LDS at five features
+#define ROLL_THREADS 256
+#define ROLL_WAVES (ROLL_THREADS / 64)
+#define ROLL_PER_LANE (ROLL_SLICE / ROLL_THREADS)
+typedef float roll_f4 __attribute__((ext_vector_type(4)));
+
+extern "C" int64_t mst_roll_slices(int64_t n_cells) {
+    if (n_cells < 1 || n_cells >= ((int64_t)1 << 31)) return MST_ERR_ARG;
+    return (n_cells + ROLL_SLICE - 1) / ROLL_SLICE;
+}
+
+// Stages slice blockIdx.x into LDS and returns its number of cells (the last slice is ragged).  g = flat float index + shift,
+// shift = floats between the previous 16-byte boundary and x, so that g = 0 (mod 4) is a 16-byte-aligned address whatever the
+// alignment of x.  img4 holds g in [gb, gb + ROLL_SLICE * NFEAT + 4); cell c of the slice starts at float shift + c * NFEAT of it.
+// Only floats of x are read: a group of four that is not wholly inside the slice takes scalar loads.
+template <int NFEAT>
+__device__ __forceinline__ int roll_stage(const float* x, int64_t n_cells, int shift, roll_f4* img4) {
+    float* img = reinterpret_cast<float*>(img4);
+    const MST_GLOBAL_AS float* xg = (const MST_GLOBAL_AS float*)x;
+    const int64_t c0 = (int64_t)blockIdx.x * ROLL_SLICE;
+    const int cells = (int)(n_cells - c0 < ROLL_SLICE ? n_cells - c0 : ROLL_SLICE);
+    const int64_t gb = c0 * NFEAT, g0 = gb + shift, g1 = g0 + (int64_t)cells * NFEAT;
+    for (int i = threadIdx.x; i < ROLL_SLICE * NFEAT / 4 + 1; i += ROLL_THREADS) {
+        const int64_t g = gb + 4 * i;
+        if (g >= g0 && g + 4 <= g1) {
+            img4[i] = *reinterpret_cast<const MST_GLOBAL_AS roll_f4*>(xg + (g - shift));
+        } else {
+            for (int j = 0; j < 4; ++j)
+                if (g + j >= g0 && g + j < g1) img[4 * i + j] = xg[g + j - shift];
+        }
+    }
+    __syncthreads();
+    return cells;
+}
+
+// Is cell `c` a record, and with which features?  MST_ROLL_NONZERO: any non-zero bit pattern (-0.0 and NaN count), features
+// verbatim.  MST_ROLL_HARD: hard_output_kernel's operations in its order (style/model.py:818-832); a record when the hard
+// velocity is non-zero, so a NaN velocity is dropped as hard_output zeroes it.
+template <int NFEAT>
+__device__ __forceinline__ bool roll_record(const float* c, int mode, float (&f)[NFEAT]) {
+    if (mode == MST_ROLL_NONZERO) {
+        unsigned any = 0;
+#pragma unroll
+        for (int k = 0; k < NFEAT; ++k) {
+            f[k] = c[k];
+            any |= __float_as_uint(c[k]);
+        }
+        return any != 0;
+    }
+    f[0] = c[0];
+    f[1] = c[1] > .01f ? c[1] : 0.f;
+    if (NFEAT > 2) {
+        const float mx = fmaxf(c[2], fmaxf(c[3], c[4]));
+#pragma unroll
+        for (int a = 2; a < NFEAT; ++a) f[a] = (c[a] == mx && c[a] > .1f) ? 1.f : 0.f;
+    }
+    return c[1] > .01f;
+}
+
+// inclusive scan over the 64 lanes of a wave
+__device__ __forceinline__ int roll_wave_scan(int v, int lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int t = __shfl(v, lane >= d ? lane - d : lane);
+        if (lane >= d) v += t;
+    }
+    return v;
+}
+
+// Wave w owns cells [256 w, 256 w + 256) of the slice and lane l the cells 256 w + 64 j + l, j < 4: neighbouring lanes read
+// neighbouring cells, 5 (or 2) floats apart in LDS — an odd stride is conflict-free for ds_read_b32, the unpitched stride of 2
+// costs two LDS cycles per read.
+#define ROLL_CELL(wave, j, lane) ((wave) * (64 * ROLL_PER_LANE) + (j) * 64 + (lane))
+
+template <int NFEAT>
+__global__ __launch_bounds__(ROLL_THREADS) void roll_count_kernel(const float* x, int64_t n_cells, int shift, int mode, int32_t* ws) {
+    __shared__ roll_f4 img4[ROLL_SLICE * NFEAT / 4 + 1];
+    __shared__ int wtot[ROLL_WAVES];
+    const int cells = roll_stage<NFEAT>(x, n_cells, shift, img4);
+    const float* img = reinterpret_cast<const float*>(img4) + shift;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int n = 0;
+#pragma unroll
+    for (int j = 0; j < ROLL_PER_LANE; ++j) {
+        const int c = ROLL_CELL(wave, j, lane);
+        float f[NFEAT];
+        if (c < cells && roll_record<NFEAT>(img + c * NFEAT, mode, f)) ++n;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
+    if (lane == 0) wtot[wave] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int total = 0;
+        for (int w = 0; w < ROLL_WAVES; ++w) total += wtot[w];
+        ws[blockIdx.x] = total;
+    }
+}
+
+// one workgroup: ws[0, n) from per-slice counts to their exclusive prefix, in place and in order; ws[n] = the total
+__global__ __launch_bounds__(ROLL_THREADS) void roll_scan_kernel(int32_t* ws, int n) {
+    __shared__ int wtot[ROLL_WAVES];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    int carry = 0;
+    for (int base = 0; base < n; base += ROLL_THREADS * 4) {       // workgroup-uniform
+        const int i0 = base + tid * 4;
+        int v[4], sum = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            v[j] = i0 + j < n ? ws[i0 + j] : 0;
+            sum += v[j];
+        }
+        const int incl = roll_wave_scan(sum, lane);
+        if (lane == 63) wtot[wave] = incl;
+        __syncthreads();
+        int run = carry + incl - sum, total = 0;
+        for (int w = 0; w < ROLL_WAVES; ++w) {
+            if (w < wave) run += wtot[w];
+            total += wtot[w];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (i0 + j < n) ws[i0 + j] = run;
+            run += v[j];
+        }
+        carry += total;
+        __syncthreads();                                           // wtot is rewritten by the next round
+    }
+    if (tid == 0) ws[n] = carry;
+}
+
+template <int NFEAT>
+__global__ __launch_bounds__(ROLL_THREADS) void roll_emit_kernel(const float* x, int64_t n_cells, int shift, int mode, const int32_t* ws,
+                                                                 int64_t capacity, int32_t* cells_out, float* feats) {
+    __shared__ roll_f4 img4[ROLL_SLICE * NFEAT / 4 + 1];
+    __shared__ int32_t rec[ROLL_SLICE];
+    __shared__ int wtot[ROLL_WAVES];
+    const int base = ws[blockIdx.x];                               // records in the slices before this one
+    if (base < 0 || base >= capacity || ws[blockIdx.x + 1] == base) return;     // nothing of this slice is stored (workgroup-uniform)
+    const int cells = roll_stage<NFEAT>(x, n_cells, shift, img4);
+    float* img = reinterpret_cast<float*>(img4);
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    // one byte per j: is the lane's j-th cell a record?  Scanned over the wave as one integer (a byte counts to 64 at most).
+    float f[ROLL_PER_LANE][NFEAT];
+    int mine = 0;
+#pragma unroll
+    for (int j = 0; j < ROLL_PER_LANE; ++j) {
+        const int c = ROLL_CELL(wave, j, lane);
+        if (c < cells && roll_record<NFEAT>(img + shift + c * NFEAT, mode, f[j])) mine |= 1 << (8 * j);
+    }
+    const int incl = roll_wave_scan(mine, lane);
+    const int tot = __shfl(incl, 63);
+    if (lane == 0) wtot[wave] = (tot & 255) + ((tot >> 8) & 255) + ((tot >> 16) & 255) + ((tot >> 24) & 255);
+    __syncthreads();                                               // and every lane holds its cells in registers: the image may be overwritten
+    int rank = 0, count = 0;
+    for (int w = 0; w < ROLL_WAVES; ++w) {
+        if (w < wave) rank += wtot[w];
+        count += wtot[w];
+    }
+    const int32_t c0 = (int32_t)((int64_t)blockIdx.x * ROLL_SLICE);
+#pragma unroll
+    for (int j = 0; j < ROLL_PER_LANE; ++j) {                      // cell order within the wave: j, then lane
+        if ((mine >> (8 * j)) & 1) {
+            const int r = rank + ((incl >> (8 * j)) & 255) - 1;
+            rec[r] = c0 + ROLL_CELL(wave, j, lane);
+#pragma unroll
+            for (int k = 0; k < NFEAT; ++k) img[r * NFEAT + k] = f[j][k];
+        }
+        rank += (tot >> (8 * j)) & 255;
+    }
+    __syncthreads();
+    const int64_t room = capacity - base;                          // records of rank >= capacity are dropped, never stored
+    const int keep = count < room ? count : (int)room;
+    for (int i = tid; i < keep; i += ROLL_THREADS) cells_out[base + i] = rec[i];
+    float* dst = feats + (int64_t)base * NFEAT;
+    for (int i = tid; i < keep * NFEAT; i += ROLL_THREADS) dst[i] = img[i];
+}
+
+static bool roll_args_ok(const float* x, int64_t n_cells, int32_t nfeat, int32_t mode) {
+    return x && n_cells >= 1 && n_cells < ((int64_t)1 << 31) && (nfeat == 5 || nfeat == 2) &&
+           (mode == MST_ROLL_NONZERO || mode == MST_ROLL_HARD) && !((uintptr_t)x & 3);
+}
+
+extern "C" int32_t mst_roll_count(const float* x, int64_t n_cells, int32_t nfeat, int32_t mode, int32_t* ws, mst_stream stream) {
+    if (!roll_args_ok(x, n_cells, nfeat, mode) || !ws) return MST_ERR_ARG;
+    const int shift = (int)(((uintptr_t)x & 15) / 4);
+    const unsigned nb = (unsigned)mst_roll_slices(n_cells);
+    hipStream_t s = (hipStream_t)stream;
+    if (nfeat == 5)
+        hipLaunchKernelGGL(roll_count_kernel<5>, dim3(nb), dim3(ROLL_THREADS), 0, s, x, n_cells, shift, (int)mode, ws);
+    else
+        hipLaunchKernelGGL(roll_count_kernel<2>, dim3(nb), dim3(ROLL_THREADS), 0, s, x, n_cells, shift, (int)mode, ws);
+    hipLaunchKernelGGL(roll_scan_kernel, dim3(1), dim3(ROLL_THREADS), 0, s, ws, (int)nb);
+    return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
+}
+
+extern "C" int32_t mst_roll_compact(const float* x, int64_t n_cells, int32_t nfeat, int32_t mode, const int32_t* ws, int64_t capacity,
+                                    int32_t* cells, float* feats, mst_stream stream) {
+    if (!roll_args_ok(x, n_cells, nfeat, mode) || !ws || !cells || !feats || capacity < 0) return MST_ERR_ARG;
+    if (capacity == 0) return MST_OK;
+    const int shift = (int)(((uintptr_t)x & 15) / 4);
+    const unsigned nb = (unsigned)mst_roll_slices(n_cells);
+    hipStream_t s = (hipStream_t)stream;
+    if (nfeat == 5)
+        hipLaunchKernelGGL(roll_emit_kernel<5>, dim3(nb), dim3(ROLL_THREADS), 0, s, x, n_cells, shift, (int)mode, ws, capacity, cells, feats);
+    else
+        hipLaunchKernelGGL(roll_emit_kernel<2>, dim3(nb), dim3(ROLL_THREADS), 0, s, x, n_cells, shift, (int)mode, ws, capacity, cells, feats);
+    return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
+}

@@ -44,6 +44,7 @@ class PlanOptions(C.Structure):
 
 
 DEV_LSTM_TIMEOUT = 1        # mst_amd.h MST_DEV_LSTM_TIMEOUT
+ROLL_NONZERO, ROLL_HARD = 0, 1      # mst_amd.h MST_ROLL_*: record modes of mst_roll_count / mst_roll_compact
 
 
 def describe_status(word):
@@ -106,6 +107,9 @@ _SIGS = {
                                    C.c_int32, C.c_double, C.c_int32, _P]),
     'mst_hard_output': (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P]),
     'mst_clip_scatter': (C.c_int32, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _P, _P]),
+    'mst_roll_slices': (C.c_int64, [C.c_int64]),
+    'mst_roll_count': (C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
+    'mst_roll_compact': (C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P]),
     'mst_plan_step_count': (C.c_int32, [_P, C.c_int32, C.c_int32]),
     'mst_plan_step_info': (C.c_int32, [_P, C.c_int32, C.c_int32, _P]),
     'mst_plan_step_carried': (C.c_int32, [_P, C.c_int32, C.c_int32, _P]),
@@ -178,6 +182,27 @@ class Native:
         addr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()
         check(self.lib.mst_clip_scatter(addr(cells), addr(feats), addr(counts), int(capacity), int(n_clips), int(n_cells), int(nfeat),
                                         addr(out), stream), 'mst_clip_scatter')
+
+    def roll_slices(self, n_cells):
+        """mst_roll_slices: slices the compaction kernels cut `n_cells` into; the workspace of roll_count holds one int32 more."""
+        n = self.lib.mst_roll_slices(int(n_cells))
+        if n <= 0:
+            raise MstError(f'mst_roll_slices({n_cells}): need 1 <= n_cells < 2**31')
+        return n
+
+    def roll_count(self, x, n_cells, nfeat, mode, ws, stream=None):
+        """mst_roll_count: count the records of the dense roll `x` (n_cells x nfeat floats) per slice and scan the counts into
+        `ws` (int32, roll_slices(n_cells) + 1): ws[s] = records before slice s, ws[-1] = the total.  `mode`: ROLL_NONZERO or
+        ROLL_HARD.  `x`, `ws` are tensors on one device or raw addresses.  Enqueue-only."""
+        addr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()
+        check(self.lib.mst_roll_count(addr(x), int(n_cells), int(nfeat), int(mode), addr(ws), stream), 'mst_roll_count')
+
+    def roll_compact(self, x, n_cells, nfeat, mode, ws, capacity, cells, feats, stream=None):
+        """mst_roll_compact: after roll_count on the same `x`, write the records of rank < `capacity` to `cells` (int32) and
+        `feats` (float32, capacity x nfeat) in ascending cell order.  Tensors on x's device or raw addresses.  Enqueue-only."""
+        addr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()
+        check(self.lib.mst_roll_compact(addr(x), int(n_cells), int(nfeat), int(mode), addr(ws), int(capacity), addr(cells), addr(feats),
+                                        stream), 'mst_roll_compact')
 
     def plan(self, dims, device):
         opts = options_from_env()

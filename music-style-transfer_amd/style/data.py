@@ -14,7 +14,7 @@ from style.midi import load_midi_from_file, is_pitched, program2instrument, prog
 from style.midi_conversion import read_midi, ChannelConverter, NoteTable, _key_weights
 from style.model import device
 from style.scales import key_names, get_scale, major_mode
-from style.sparse import SparseRoll, sparsify          # noqa: F401  (part of this module's surface)
+from style.sparse import SparseRoll, sparsify, compact # noqa: F401  (part of this module's surface)
 
 included_instruments = popular_instruments
 instrument_groups = [program2group[p] for p in included_instruments]

@@ -421,6 +421,32 @@ class ChannelConverter:
         qchannel['notes'] = notes
         return qchannel
 
+    def records2qchannel(self, channel_info, roll_shape, cells, feats):
+        """`vchannel2qchannel` (:518-566) from the note records of the hard roll instead of the roll: `cells` are the flat
+        indices (ascending, C order) into one channel's (R, T, 10, rows) roll of `roll_shape` — with or without its feature
+        axis — whose velocity is non-zero, `feats` their features.  Same NoteTable: same order, values and dtypes."""
+        pitched = is_pitched(channel_info['instrument_id'])
+        feats = np.asarray(feats)
+        grid = tuple(int(d) for d in roll_shape)
+        grid = grid[:-1] if len(grid) == 5 else grid
+        if len(grid) != 4 or feats.ndim != 2 or feats.shape[1] != self.n_features(pitched):
+            raise ValueError(f'records of a roll of shape {tuple(roll_shape)} with features {feats.shape}')
+        bar, beat, fraction, row = np.unravel_index(np.asarray(cells, dtype=np.int64), grid)
+        tpb = self.info['ticks_per_beat']
+        notes = NoteTable(len(bar), bar=bar, beat=beat, fraction=fraction, velocity=feats[:, 1],
+                          qduration=(feats[:, 0] * tpb).astype(np.int64))
+        if pitched:
+            flat, natural, sharp = feats[:, 2] != 0, feats[:, 3] != 0, feats[:, 4] != 0
+            notes.accidental = np.where(flat, FLAT, np.where(natural, NATURAL, np.where(sharp, SHARP, NATURAL)))
+            notes.scale_degree = row % 7 + 1
+            notes.scale_octave = row // 7
+        else:
+            notes.accidental = np.full(len(bar), NO_ACCIDENTAL, np.int64)
+            notes.note_id = row + self.min_percussion
+        qchannel = dict(channel_info)
+        qchannel['notes'] = notes
+        return qchannel
+
     def qchannel2channel(self, channel_info, qchannel):
         """Notes -> note_on/note_off stream ordered by tick (stable over on0, off0, on1, off1, ...)."""
         notes = qchannel['notes']
@@ -451,6 +477,9 @@ class ChannelConverter:
 
     def vchannel2channel(self, channel_info, vchannel):
         return self.qchannel2channel(channel_info, self.vchannel2qchannel(channel_info, vchannel))
+
+    def records2channel(self, channel_info, roll_shape, cells, feats):
+        return self.qchannel2channel(channel_info, self.records2qchannel(channel_info, roll_shape, cells, feats))
 
     @property
     def mode(self):

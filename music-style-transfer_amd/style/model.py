@@ -21,7 +21,7 @@ import torch
 from torch import nn
 
 from style import _native
-from style.sparse import SparseRoll, scatter_packed
+from style.sparse import SparseRoll, scatter_packed, compact
 from style.utils.pytorch import Distributed, LSTM
 
 epsilon = 1e-7
@@ -801,3 +801,12 @@ def hard_output(x):
         with torch.no_grad():
             x[..., 1] = work[..., 1].to(x.dtype)
     return out
+
+
+def hard_output_sparse(x):
+    """`hard_output` (style/model.py:818-832) as sorted note records: a host `style.data.SparseRoll` of the cells whose hard
+    velocity is non-zero, with their hard features — what the MIDI decoder reads of the dense result.  The records are built on
+    the GPU (mst_roll_count / mst_roll_compact) and only they are downloaded.  Unlike `hard_output` it leaves `x` untouched."""
+    if x.device.type != 'cuda':
+        raise _native.MstError('hard_output_sparse needs a GPU tensor; there is no CPU fallback')
+    return compact(x, 'hard')

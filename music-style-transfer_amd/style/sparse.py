@@ -30,13 +30,7 @@ class SparseRoll:
     (default: when a GPU is present)."""
 
     def __init__(self, cells, feats, shape, pin=None):
-        shape = tuple(int(d) for d in shape)
-        if len(shape) < 2 or shape[-1] not in (2, 5):
-            raise ValueError(f'shape {shape}: the last axis holds the 5 pitched or 2 unpitched note features')
-        nfeat = shape[-1]
-        n_cells = int(np.prod(shape[:-1], dtype=np.int64))
-        if not 1 <= n_cells < 2 ** 31:
-            raise ValueError(f'shape {shape}: {n_cells} cells, need 1 <= cells < 2**31')
+        shape, nfeat, n_cells = self._geometry(shape)
         cells = np.ascontiguousarray(torch.as_tensor(cells).numpy() if torch.is_tensor(cells) else cells)
         feats = np.ascontiguousarray(torch.as_tensor(feats).numpy() if torch.is_tensor(feats) else feats)
         if cells.ndim != 1 or cells.dtype.kind not in 'iu':
@@ -45,22 +39,55 @@ class SparseRoll:
         feats = feats.reshape(n, nfeat) if feats.size == n * nfeat else feats
         if feats.shape != (n, nfeat):
             raise ValueError(f'feats: shape {feats.shape}, expected {(n, nfeat)}')
-        if n:
+        self._check_cells(cells, n_cells)
+        if pin is None:
+            pin = torch.cuda.is_available()
+        self._adopt(torch.zeros(packed_words(n, nfeat), dtype=torch.int32, pin_memory=bool(pin)), n, shape, nfeat, n_cells)
+        self.packed[0] = n
+        self.cells.numpy()[:] = cells
+        self.feats.numpy()[:] = feats.astype(np.float32, copy=False)
+
+    @staticmethod
+    def _geometry(shape):
+        shape = tuple(int(d) for d in shape)
+        if len(shape) < 2 or shape[-1] not in (2, 5):
+            raise ValueError(f'shape {shape}: the last axis holds the 5 pitched or 2 unpitched note features')
+        n_cells = int(np.prod(shape[:-1], dtype=np.int64))
+        if not 1 <= n_cells < 2 ** 31:
+            raise ValueError(f'shape {shape}: {n_cells} cells, need 1 <= cells < 2**31')
+        return shape, shape[-1], n_cells
+
+    @staticmethod
+    def _check_cells(cells, n_cells):
+        if len(cells):
             c64 = cells.astype(np.int64)
             if c64.min() < 0 or c64.max() >= n_cells:
                 raise ValueError(f'cells out of range [0, {n_cells})')
             if np.any(np.diff(c64) <= 0):
                 raise ValueError('cells must be strictly ascending (sorted, no duplicates)')
-        if pin is None:
-            pin = torch.cuda.is_available()
+
+    def _adopt(self, packed, n, shape, nfeat, n_cells):
         self.shape, self.nfeat, self.n_cells, self.count = shape, nfeat, n_cells, n
-        self.packed = torch.zeros(packed_words(n, nfeat), dtype=torch.int32, pin_memory=bool(pin))
-        self.packed[0] = n
+        self.packed = packed
         at = HEADER + _cells_words(n)
-        self.cells = self.packed[HEADER:HEADER + n]
-        self.feats = self.packed[at:at + n * nfeat].view(torch.float32).view(n, nfeat)
-        self.cells.numpy()[:] = cells
-        self.feats.numpy()[:] = feats.astype(np.float32, copy=False)
+        self.cells = packed[HEADER:HEADER + n]
+        self.feats = packed[at:at + n * nfeat].view(torch.float32).view(n, nfeat)
+
+    @classmethod
+    def from_packed(cls, packed, shape):
+        """Adopt `packed` — a contiguous host int32 tensor in the packed layout, its header word holding the count — as the
+        records of a roll of `shape`: no copy, `cells` / `feats` are views of it.  The same validation as the constructor."""
+        shape, nfeat, n_cells = cls._geometry(shape)
+        if not torch.is_tensor(packed) or packed.dtype != torch.int32 or packed.dim() != 1 or packed.device.type != 'cpu' or \
+                not packed.is_contiguous() or packed.numel() < HEADER:
+            raise ValueError('packed: a contiguous 1-d int32 host tensor with the 4-word header')
+        n = int(packed[0])
+        if n < 0 or packed.numel() != packed_words(n, nfeat):
+            raise ValueError(f'packed: {packed.numel()} words do not hold {n} records of {nfeat} features')
+        roll = cls.__new__(cls)
+        roll._adopt(packed, n, shape, nfeat, n_cells)
+        cls._check_cells(roll.cells.numpy(), n_cells)
+        return roll
 
     def __repr__(self):
         return f'SparseRoll(shape={self.shape}, records={self.count})'
@@ -105,3 +132,41 @@ def sparsify(roll, pin=None):
     bits = x.view(np.uint32).reshape(-1, x.shape[-1])
     cells = np.flatnonzero(bits.any(axis=1))
     return SparseRoll(cells.astype(np.int32), x.reshape(bits.shape)[cells], x.shape, pin=pin)
+
+
+_MODES = {'nonzero': _native.ROLL_NONZERO, 'hard': _native.ROLL_HARD}
+
+
+def compact(x, mode='nonzero', pin=None, native=None):
+    """Dense roll ON THE DEVICE (feature axis last) -> SparseRoll on the host, the inverse of `SparseRoll.to_dense`: the records
+    are built on x's device by mst_roll_count / mst_roll_compact and only they are downloaded.  mode='nonzero': every cell with
+    a non-zero bit pattern, features verbatim — `sparsify(x)`.  mode='hard': the cells hard_output (style/model.py:818-832)
+    leaves with a non-zero velocity, carrying its hard features; `x` is not modified.  One 4-byte read of the count is the only
+    synchronisation before the one copy of the records (into pinned memory when `pin`, default: for a GPU tensor).
+    `native`: another build of the C ABI (tests: the CPU interpreter build, on CPU tensors)."""
+    if mode not in _MODES:
+        raise ValueError(f'mode {mode!r}: expected one of {sorted(_MODES)}')
+    native = native or _native.get()
+    shape = tuple(x.shape)
+    x = x.detach()
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        x = x.float().contiguous()
+    nfeat = shape[-1] if len(shape) >= 2 else 0
+    if nfeat not in (2, 5) or x.numel() == 0:
+        raise ValueError(f'shape {shape}: the last axis holds the 5 pitched or 2 unpitched note features')
+    n_cells = x.numel() // nfeat
+    stream = _native.current_stream(x.device)
+    ws = torch.empty(native.roll_slices(n_cells) + 1, dtype=torch.int32, device=x.device)
+    native.roll_count(x, n_cells, nfeat, _MODES[mode], ws, stream)
+    n = int(ws[-1])                                   # the only synchronisation: 4 bytes
+    records = torch.empty(packed_words(n, nfeat), dtype=torch.int32, device=x.device)
+    base = records.data_ptr() + 4 * HEADER
+    native.roll_compact(x, n_cells, nfeat, _MODES[mode], ws, n, base, base + 4 * _cells_words(n), stream)
+    if pin is None:
+        pin = x.device.type == 'cuda'
+    packed = torch.empty(records.numel(), dtype=torch.int32, pin_memory=bool(pin))
+    packed.copy_(records)
+    packed[:HEADER] = 0
+    packed[0] = n
+    packed[HEADER + n:HEADER + _cells_words(n)] = 0   # the padding behind the cells
+    return SparseRoll.from_packed(packed, shape)

@@ -7,7 +7,9 @@ over the HIP model.  Forward only, one pass per song:
 
 The per-song host decisions are split out so they can be tested without a GPU:
 `select_instruments` (top-n programs out of the 41 predicted logits, :105-116), `combine_info` (:134-142)
-and `decode_rolls` (rolls -> MidiFile, the host half of `decode_midi`).  Behaviour kept from the
+and `decode_rolls` (rolls -> MidiFile, the host half of `decode_midi`).  With `sparse_output=True` the dense
+hard rolls never reach the host: `hard_output_sparse` compacts them to note records on the GPU and
+`decode_records` writes the same file from those, byte for byte.  Behaviour kept from the
 reference: songs are cut to `1000 // C` bars for the encoder (:69) while `original/*.mid` is written
 from the full-length rolls; `apply_style` overwrites `info['tempo']` and `info['scale']['mode']` of the
 dict it is given (the scale dict is shared with the style song's info); an existing output directory is
@@ -23,11 +25,11 @@ from style.data import (included_instruments, get_input, prepare_input, percussi
                         _instrument_categories)
 from style.midi import load_midi_from_file, create_midi
 from style.midi_conversion import ChannelConverter, read_midi
-from style.model import device, hard_output
+from style.model import device, hard_output, hard_output_sparse
 from style.scales import major_mode, minor_mode
 
 
-def transfer_style(model, composition_path, style_paths, output_path):
+def transfer_style(model, composition_path, style_paths, output_path, sparse_output=False):
     composition_name = os.path.splitext(os.path.basename(composition_path))[0]
     composition_input = get_model_input(composition_path)
     _, (composition_info, composition_pitched, _, composition_instruments, composition_unpitched) = composition_input
@@ -36,19 +38,19 @@ def transfer_style(model, composition_path, style_paths, output_path):
     output_path = os.path.join(output_path, composition_name)
 
     save(composition_cc, composition_pitched, composition_unpitched, composition_instruments,
-         os.path.join(output_path, f'original/{composition_name}.mid'))
+         os.path.join(output_path, f'original/{composition_name}.mid'), sparse_output=sparse_output)
     apply_style(model, composition_info, style_, melody, rhythm, len(composition_instruments),
-                os.path.join(output_path, f'{composition_name} (reconstructed).mid'))
+                os.path.join(output_path, f'{composition_name} (reconstructed).mid'), sparse_output=sparse_output)
     for style_path in style_paths:
         style_name = os.path.splitext(os.path.basename(style_path))[0]
         style_input = get_model_input(style_path)
         _, (style_info, style_pitched, _, style_instruments, style_unpitched) = style_input
         style, _, _ = extract_style(model, style_input)
         save(ChannelConverter(style_info), style_pitched, style_unpitched, style_instruments,
-             os.path.join(output_path, f'original/{style_name}.mid'))
+             os.path.join(output_path, f'original/{style_name}.mid'), sparse_output=sparse_output)
         info = combine_info(style_info=style_info, melody_info=composition_info)
         apply_style(model, info, style, melody, rhythm, len(style_instruments),
-                    os.path.join(output_path, f'{composition_name} ({style_name} style).mid'))
+                    os.path.join(output_path, f'{composition_name} ({style_name} style).mid'), sparse_output=sparse_output)
 
 
 def get_model_input(path):
@@ -75,7 +77,7 @@ def channel_slots(instruments):
     return pitched, {'channel_id': 9, 'instrument_id': -1}
 
 
-def save(cc, pitched_channels, unpitched_channels, instruments, save_path):
+def save(cc, pitched_channels, unpitched_channels, instruments, save_path, sparse_output=False):
     channels_info, unpitched_info = channel_slots(instruments)
     channels_info = channels_info[:pitched_channels.shape[1]]     # (for numpy rolls shape[1] is the bar count: reference quirk)
     os.makedirs(os.path.dirname(save_path) or '.', exist_ok=True)
@@ -83,7 +85,7 @@ def save(cc, pitched_channels, unpitched_channels, instruments, save_path):
         pitched_channels = torch.tensor(pitched_channels, dtype=torch.float).unsqueeze(0).to(device)
         if unpitched_channels is not None:
             unpitched_channels = torch.tensor(unpitched_channels, dtype=torch.float).unsqueeze(0).to(device)
-    mid = decode_midi(cc, channels_info, pitched_channels, unpitched_info, unpitched_channels)
+    mid = decode_midi(cc, channels_info, pitched_channels, unpitched_info, unpitched_channels, sparse_output=sparse_output)
     mid.save(save_path)
 
 
@@ -99,7 +101,7 @@ def select_instruments(instruments_pred, n_instruments):
     return programs, unpitched
 
 
-def apply_style(model, info, style, melody, rhythm, n_instruments, save_path):
+def apply_style(model, info, style, melody, rhythm, n_instruments, save_path, sparse_output=False):
     with torch.no_grad():
         instruments_pred, mode, bpm = model.predict_song_info(style, rhythm)
     info['tempo'] = smf.bpm2tempo(round(float(bpm)))
@@ -109,7 +111,7 @@ def apply_style(model, info, style, melody, rhythm, n_instruments, save_path):
     instruments_features = torch.tensor(encode_instruments(instruments), dtype=torch.float).to(device).unsqueeze(0)
     with torch.no_grad():
         pitched_pred, unpitched_pred = model.apply_style(style, melody, rhythm, instruments_features, unpitched)
-    save(cc, pitched_pred, unpitched_pred, instruments, save_path)
+    save(cc, pitched_pred, unpitched_pred, instruments, save_path, sparse_output=sparse_output)
 
 
 def combine_info(style_info, melody_info):
@@ -131,7 +133,33 @@ def decode_rolls(channel_converter, channels_info, pitched_rolls, unpitched_chan
     return create_midi(channel_converter.info, *channels, max_delta_time=1)
 
 
-def decode_midi(channel_converter, channels_info, pitched_channels, unpitched_channel_info=None, unpitched_channels=None):
+def split_records(pitched_records):
+    """Per channel of a pitched SparseRoll of (1, C, R, T, 10, 56, 5): (cells within the channel's roll, feats), in channel order.
+    The records are sorted by cell, so the channels are runs of them, cut at multiples of R * T * 10 * 56 cells."""
+    n_channels = pitched_records.shape[1]
+    per_channel = int(np.prod(pitched_records.shape[2:-1], dtype=np.int64))
+    cells, feats = pitched_records.cells.numpy(), pitched_records.feats.numpy()
+    cuts = np.searchsorted(cells, per_channel * np.arange(n_channels + 1, dtype=np.int64))
+    return [(cells[a:b] - c * per_channel, feats[a:b]) for c, (a, b) in enumerate(zip(cuts[:-1], cuts[1:]))]
+
+
+def decode_records(channel_converter, channels_info, pitched_records, unpitched_channel_info=None, unpitched_records=None):
+    """`decode_rolls` from the note records of the hard rolls (`style.data.SparseRoll` of (1, C, R, T, 10, 56, 5) /
+    (1, 1, R, T, 10, 47, 2)); the channels kept are those `zip(channels_info, pitched_rolls)` keeps."""
+    channels = [channel_converter.records2channel(channel_info, pitched_records.shape[2:], cells, feats)
+                for channel_info, (cells, feats) in zip(channels_info, split_records(pitched_records))]
+    if unpitched_records is not None:
+        channels.append(channel_converter.records2channel(unpitched_channel_info, unpitched_records.shape[2:],
+                                                          unpitched_records.cells.numpy(), unpitched_records.feats.numpy()))
+    return create_midi(channel_converter.info, *channels, max_delta_time=1)
+
+
+def decode_midi(channel_converter, channels_info, pitched_channels, unpitched_channel_info=None, unpitched_channels=None,
+                sparse_output=False):
+    if sparse_output:
+        pitched_records = hard_output_sparse(pitched_channels)
+        unpitched_records = None if unpitched_channels is None else hard_output_sparse(unpitched_channels)
+        return decode_records(channel_converter, channels_info, pitched_records, unpitched_channel_info, unpitched_records)
     pitched_rolls = hard_output(pitched_channels).cpu().detach().numpy()[0]
     unpitched_roll = None
     if unpitched_channels is not None:
