@@ -199,6 +199,52 @@ int32_t mst_adam_step2(float* params, float* grads, float* grads2, float* exp_av
                        float* state, double lr0, double beta1, double beta2, double eps,
                        int32_t step_size, double gamma, int32_t zero_grad, mst_stream stream);
 
+/* ---- guarded optimizer step: global gradient-norm clipping and the skip of a non-finite step, decided on the device.
+ * No reference counterpart: the reference only asserts on a NaN loss (train-model.py:121), and sums its gradients over
+ * iter_size songs (train-model.py:126,151-153), so their scale grows with every accumulated clip.
+ * The effective gradient is grads, or grads + grads2 formed in fp32 exactly as the step forms it.  Its squares are summed in
+ * double: the flat buffer is cut into slices of a fixed element count, one partial per slice in `scratch`
+ * (mst_grad_guard_scratch_bytes, 8-byte aligned), and one workgroup adds the partials in a fixed order.  The number of
+ * partials depends on n alone; there are no atomics and no workgroup waits for another: the same bits on every run.
+ * The gradient buffers need float alignment only.
+ *
+ * The guarded step, three launches (one more than the plain step), enqueue-only on `stream` (no allocation, no host
+ * synchronisation, capturable as a single chain):
+ *   norm      = (float)sqrt(sum of squares)
+ *   nonfinite = norm is inf or NaN — the test is applied to the fp32 norm, so finite gradients whose norm overflows fp32 count
+ *   coef      = min(1, (float)max_norm * (1 / (norm + 1e-6f))) in fp32: max_norm / (total_norm + 1e-6) of
+ *               torch.nn.utils.clip_grad_norm_ in the order torch evaluates it (a Python float divided by a tensor is the
+ *               reciprocal times the float), so the clipped gradient equals torch's bit for bit given the same norm;
+ *               1 when max_norm <= 0 or +inf (no clipping) and 1 when nonfinite
+ *   skip      = skip_nonfinite && nonfinite
+ * then the step of the plain entry points on the gradient (grads [+ grads2]) * coef, the product rounded to fp32 before it
+ * enters Adam's arithmetic: exactly "clip, then the plain step".  With coef = 1 it is the plain step, bit for bit.
+ * A skip leaves params, exp_avg, exp_avg_sq and state bit-unchanged — the step count and the StepLR schedule do not
+ * advance — and still zeroes grads / grads2 when zero_grad is set.
+ * With skip_nonfinite = 0 a non-finite norm gives the plain, unguarded step (coef = 1).  This differs from
+ * torch.nn.utils.clip_grad_norm_, whose NaN coefficient would turn every gradient into NaN.
+ *
+ * guard: MST_GUARD_WORDS device floats, zeroed once by the caller, rewritten by every call:
+ *   [0] norm of this call (may be inf / NaN)       [3] calls skipped so far
+ *   [1] coefficient applied (1 = not clipped,      [4] calls clipped so far (coef < 1)
+ *       0 when skipped)                            [5] largest finite norm so far
+ *   [2] 1 if this call was skipped, else 0         [6..7] 0
+ * Counts are floats, exact to 2^24, like state[0].
+ * MST_ERR_ARG: null pointer other than grads2, n <= 0, step_size <= 0, NaN max_norm, scratch not 8-byte aligned. */
+#define MST_GUARD_WORDS 8
+int64_t mst_grad_guard_scratch_bytes(int64_t n);   /* bytes of partials for n elements; <= 0 on a bad n */
+/* *norm (one device float) = L2 norm of the effective gradient; two launches */
+int32_t mst_grad_norm(const float* grads, const float* grads2 /* NULL ok */, int64_t n, void* scratch, float* norm,
+                      mst_stream stream);
+/* diagnostic, one launch: norms[k] = L2 norm of the effective gradient over [offsets[k], offsets[k] + lengths[k]), for
+ * k < count; offsets / lengths are DEVICE arrays; same double accumulation in a fixed order, one workgroup per range */
+int32_t mst_grad_norms(const float* grads, const float* grads2 /* NULL ok */, const int64_t* offsets, const int64_t* lengths,
+                       int32_t count, float* norms, mst_stream stream);
+int32_t mst_adam_step_guarded(float* params, float* grads, float* grads2 /* NULL ok */, float* exp_avg, float* exp_avg_sq,
+                              int64_t n, float* state, float* guard, void* scratch, double lr0, double beta1, double beta2,
+                              double eps, int32_t step_size, double gamma, double max_norm /* <= 0 or +inf: no clipping */,
+                              int32_t skip_nonfinite, int32_t zero_grad, mst_stream stream);
+
 /* ---- hard_output (style/model.py:818-832): n_pos positions x nfeat (5 or 2) features.
  * Like the reference it also zeroes sub-threshold velocities of `x` in place. */
 int32_t mst_hard_output(float* x, float* out, int64_t n_pos, int32_t nfeat, mst_stream stream);

@@ -450,8 +450,7 @@ extern "C" int32_t mst_total_loss_bwd(const float* pp, const float* pt, int64_t 
 // ------------------------------------------------------------------ Adam + StepLR
 // state[0] = optimizer steps taken so far (t); the prepare kernel turns it into the step's
 // scalars in double precision exactly as torch's Python-side arithmetic does, then bumps t.
-__global__ void adam_prepare_kernel(float* state, double lr0, double b1, double b2, int step_size, double gamma) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+__device__ __forceinline__ void adam_advance(float* state, double lr0, double b1, double b2, int step_size, double gamma) {
     const int t = (int)state[0] + 1;
     const double lr = lr0 * pow(gamma, (double)((t - 1) / step_size));
     const double bc1 = 1.0 - pow(b1, (double)t);
@@ -461,13 +460,30 @@ __global__ void adam_prepare_kernel(float* state, double lr0, double b1, double 
     state[2] = (float)sqrt(bc2);
 }
 
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ g2,
-                                                   float* __restrict__ m, float* __restrict__ v, int64_t n,
-                                                   const float* __restrict__ state, float b1, float b2, float eps, int zero_grad) {
+__global__ void adam_prepare_kernel(float* state, double lr0, double b1, double b2, int step_size, double gamma) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    adam_advance(state, lr0, b1, b2, step_size, gamma);
+}
+
+// a * b rounded to fp32 on its own: hipcc contracts a product into a following add or subtract by default (and its __fmul_rn is
+// a plain product), so the product is formed with contraction off and then made opaque
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+    float r = a * b;
+    MST_PIN(r);
+    return r;
+}
+
+// GUARD: the effective gradient is scaled by the guard record's coefficient first — "clip, then the same step"
+template <bool GUARD>
+__device__ __forceinline__ void adam_update(float* __restrict__ p, float* __restrict__ g, float* __restrict__ g2,
+                                            float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                            const float* __restrict__ state, float b1, float b2, float eps, int zero_grad, float coef) {
     const float step = state[1], bc2s = state[2];
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         // g2: gradients of a second, concurrently run accumulation iteration (same sum as accumulating in place)
-        const float gi = g2 ? g[i] + g2[i] : g[i];
+        float gi = g2 ? g[i] + g2[i] : g[i];
+        if (GUARD) gi = mul_rounded(gi, coef);
         const float mi = m[i] + (gi - m[i]) * (1.f - b1);        // exp_avg.lerp_(grad, 1 - beta1)
         const float vi = v[i] * b2 + (1.f - b2) * gi * gi;
         m[i] = mi;
@@ -475,6 +491,12 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
         p[i] -= step * (mi / (sqrtf(vi) / bc2s + eps));
         if (zero_grad) { g[i] = 0.f; if (g2) g2[i] = 0.f; }
     }
+}
+
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ g2,
+                                                   float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                   const float* __restrict__ state, float b1, float b2, float eps, int zero_grad) {
+    adam_update<false>(p, g, g2, m, v, n, state, b1, b2, eps, zero_grad, 1.f);
 }
 
 static int32_t adam_launch(float* params, float* grads, float* grads2, float* exp_avg, float* exp_avg_sq, int64_t n, float* state,
@@ -501,6 +523,224 @@ extern "C" int32_t mst_adam_step2(float* params, float* grads, float* grads2, fl
                                   double gamma, int32_t zero_grad, mst_stream stream) {
     if (!grads2) return MST_ERR_ARG;
     return adam_launch(params, grads, grads2, exp_avg, exp_avg_sq, n, state, lr0, beta1, beta2, eps, step_size, gamma, zero_grad, stream);
+}
+
+// ------------------------------------------------------------------ guarded step (mst_adam_step_guarded, mst_grad_norm, mst_grad_norms)
+// Global-norm clipping and the skip of a non-finite step, decided on the device.  The flat gradient (g, or g + g2 formed in
+// fp32 as adam_update forms it) is cut into slices of GS_SLICE elements, one workgroup and one double partial each: the number
+// of partials depends on n alone, never on the device, and they are summed by one workgroup in a fixed order — no atomics, no
+// workgroup waiting for another, the same bits on every run and every device.  The squares of fp32 values are exact in double
+// (48 significant bits), so contracting square and add into an FMA changes nothing.
+#define GS_SLICE 4096            // elements per workgroup: four 16-byte loads per lane and buffer
+#define GS_THREADS 256
+#define GS_WAVES (GS_THREADS / 64)
+typedef float gs_f4 __attribute__((ext_vector_type(4)));
+
+extern "C" int64_t mst_grad_guard_scratch_bytes(int64_t n) {
+    if (n <= 0) return MST_ERR_ARG;
+    return (n + GS_SLICE - 1) / GS_SLICE * (int64_t)sizeof(double);
+}
+
+// shuffles move 32 bits: a double travels as its two halves
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        unsigned w[2];
+        __builtin_memcpy(w, &v, 8);
+        w[0] = __shfl_xor(w[0], o);
+        w[1] = __shfl_xor(w[1], o);
+        double t;
+        __builtin_memcpy(&t, w, 8);
+        v += t;
+    }
+    return v;
+}
+
+// per-lane values -> wave sums -> the four wave sums through LDS, added in wave order; the total is valid in thread 0
+__device__ __forceinline__ double gs_block_sum(double acc, double* red) {
+    acc = wave_sum_d(acc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    double total = 0.0;
+    if (threadIdx.x == 0)
+        for (int w = 0; w < GS_WAVES; ++w) total += red[w];
+    return total;
+}
+
+__device__ __forceinline__ double gs_sq4(double acc, gs_f4 x) {
+    acc += (double)x.x * (double)x.x;
+    acc += (double)x.y * (double)x.y;
+    acc += (double)x.z * (double)x.z;
+    acc += (double)x.w * (double)x.w;
+    return acc;
+}
+
+// Workgroup b owns elements [b GS_SLICE, (b + 1) GS_SLICE) of the buffer.  s = element index + shift, shift = floats between the
+// previous 16-byte boundary and g, so that s = 0 (mod 4) is a 16-byte-aligned address whatever the alignment of g; a group of
+// four that is not wholly inside the slice (the ragged head and tail of a buffer that is only float-aligned) takes scalar loads.
+// vec = 0: g2 sits at another 16-byte phase than g, every group takes scalar loads.  Lane l takes the groups l, l + 256, ... in
+// order whichever path loads them.
+__global__ __launch_bounds__(GS_THREADS) void grad_sumsq_kernel(const float* g, const float* g2, int64_t n, int shift, int vec,
+                                                                double* partials) {
+    __shared__ double red[GS_WAVES];
+    const MST_GLOBAL_AS float* a = (const MST_GLOBAL_AS float*)g;
+    const MST_GLOBAL_AS float* b = (const MST_GLOBAL_AS float*)g2;
+    const int tid = threadIdx.x;
+    const int64_t e0 = (int64_t)blockIdx.x * GS_SLICE;
+    const int64_t e1 = n - e0 < GS_SLICE ? n : e0 + GS_SLICE;
+    double acc = 0.0;
+    if (vec && shift == 0 && e1 - e0 == GS_SLICE) {                 // a whole, aligned slice: all loads in flight
+        gs_f4 x[GS_SLICE / 4 / GS_THREADS];
+#pragma unroll
+        for (int u = 0; u < GS_SLICE / 4 / GS_THREADS; ++u)
+            x[u] = *reinterpret_cast<const MST_GLOBAL_AS gs_f4*>(a + e0 + 4 * (tid + GS_THREADS * u));
+        if (b) {
+#pragma unroll
+            for (int u = 0; u < GS_SLICE / 4 / GS_THREADS; ++u)
+                x[u] += *reinterpret_cast<const MST_GLOBAL_AS gs_f4*>(b + e0 + 4 * (tid + GS_THREADS * u));
+        }
+#pragma unroll
+        for (int u = 0; u < GS_SLICE / 4 / GS_THREADS; ++u) acc = gs_sq4(acc, x[u]);
+    } else {
+        const int64_t s0 = e0 + shift, s1 = e1 + shift;
+        for (int i = tid; i < GS_SLICE / 4 + 1; i += GS_THREADS) {
+            const int64_t s = e0 + 4 * i;
+            if (vec && s >= s0 && s + 4 <= s1) {
+                gs_f4 x = *reinterpret_cast<const MST_GLOBAL_AS gs_f4*>(a + (s - shift));
+                if (b) x += *reinterpret_cast<const MST_GLOBAL_AS gs_f4*>(b + (s - shift));
+                acc = gs_sq4(acc, x);
+            } else {
+                for (int j = 0; j < 4; ++j) {
+                    if (s + j >= s0 && s + j < s1) {
+                        const float ge = b ? a[s + j - shift] + b[s + j - shift] : a[s + j - shift];
+                        acc += (double)ge * (double)ge;
+                    }
+                }
+            }
+        }
+    }
+    const double total = gs_block_sum(acc, red);
+    if (tid == 0) partials[blockIdx.x] = total;
+}
+
+// one workgroup: the partials in a fixed order (per-lane chains over q = lane, lane + 256, ..., then gs_block_sum)
+__device__ __forceinline__ double gs_total(const double* partials, int64_t np, double* red) {
+    double acc = 0.0;
+    for (int64_t q = threadIdx.x; q < np; q += GS_THREADS) acc += partials[q];
+    return gs_block_sum(acc, red);
+}
+
+__global__ __launch_bounds__(GS_THREADS) void grad_norm_final_kernel(const double* partials, int64_t np, float* norm) {
+    __shared__ double red[GS_WAVES];
+    const double s = gs_total(partials, np, red);
+    if (threadIdx.x == 0) norm[0] = (float)sqrt(s);
+}
+
+// adam_prepare_kernel of the guarded step: norm, coefficient and the skip decision into the guard record; the step counter
+// and the step's scalars advance only when the step is taken
+__global__ __launch_bounds__(GS_THREADS) void adam_prepare_guarded_kernel(float* state, float* guard, const double* partials, int64_t np,
+                                                                          double lr0, double b1, double b2, int step_size, double gamma,
+                                                                          float max_norm, int clip, int skip_nonfinite) {
+    __shared__ double red[GS_WAVES];
+    const double s = gs_total(partials, np, red);
+    if (threadIdx.x != 0) return;
+    const float norm = (float)sqrt(s);
+    const bool nonfinite = (__float_as_uint(norm) & 0x7f800000u) == 0x7f800000u;      // inf or NaN, tested on the fp32 norm
+    float coef = 1.f;
+    if (clip && !nonfinite) {
+        // torch.nn.utils.clip_grad_norm_: max_norm / (total_norm + 1e-6) clamped at 1, in the order torch evaluates it — a Python
+        // float divided by a tensor is the tensor's reciprocal times the float, two fp32 roundings (one division is 1 ulp off at
+        // g = [3, 4], max_norm = 2.5)
+        const float c = max_norm * (1.f / (norm + 1e-6f));
+        if (c < 1.f) coef = c;
+    }
+    const bool skip = skip_nonfinite && nonfinite;
+    guard[0] = norm;
+    guard[1] = skip ? 0.f : coef;
+    guard[2] = skip ? 1.f : 0.f;
+    if (skip) guard[3] += 1.f;
+    if (coef < 1.f) guard[4] += 1.f;
+    if (!nonfinite && norm > guard[5]) guard[5] = norm;
+    guard[6] = guard[7] = 0.f;
+    if (!skip) adam_advance(state, lr0, b1, b2, step_size, gamma);
+}
+
+__global__ __launch_bounds__(256) void adam_guarded_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ g2,
+                                                           float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                           const float* __restrict__ state, const float* __restrict__ guard, float b1,
+                                                           float b2, float eps, int zero_grad) {
+    if (guard[2] != 0.f) {                          // skipped: p, m, v untouched; the bad gradient is still dropped
+        if (zero_grad)
+            for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+                g[i] = 0.f;
+                if (g2) g2[i] = 0.f;
+            }
+        return;
+    }
+    adam_update<true>(p, g, g2, m, v, n, state, b1, b2, eps, zero_grad, guard[1]);
+}
+
+// one workgroup per tensor: per-lane chains over i = lane, lane + 256, ... in double, then gs_block_sum
+__global__ __launch_bounds__(GS_THREADS) void grad_norms_kernel(const float* g, const float* g2, const int64_t* offsets,
+                                                                const int64_t* lengths, float* norms) {
+    __shared__ double red[GS_WAVES];
+    const int64_t off = offsets[blockIdx.x], len = lengths[blockIdx.x];
+    const MST_GLOBAL_AS float* a = (const MST_GLOBAL_AS float*)g + off;
+    const MST_GLOBAL_AS float* b = g2 ? (const MST_GLOBAL_AS float*)g2 + off : nullptr;
+    double acc = 0.0;
+    for (int64_t i = threadIdx.x; i < len; i += GS_THREADS) {
+        const float ge = b ? a[i] + b[i] : a[i];
+        acc += (double)ge * (double)ge;
+    }
+    const double total = gs_block_sum(acc, red);
+    if (threadIdx.x == 0) norms[blockIdx.x] = (float)sqrt(total);
+}
+
+// enqueues grad_sumsq_kernel over the flat buffer; returns the number of partials, or a negative status
+static int64_t gs_launch_sumsq(const float* grads, const float* grads2, int64_t n, void* scratch, hipStream_t s) {
+    if (!grads || !scratch || n <= 0 || ((uintptr_t)scratch & 7) || ((uintptr_t)grads & 3) || ((uintptr_t)grads2 & 3)) return MST_ERR_ARG;
+    const int64_t np = (n + GS_SLICE - 1) / GS_SLICE;
+    if (np > 0x7fffffff) return MST_ERR_ARG;
+    const int shift = (int)(((uintptr_t)grads & 15) / 4);
+    const int vec = !grads2 || (((uintptr_t)grads2 & 15) == ((uintptr_t)grads & 15));
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)np), dim3(GS_THREADS), 0, s, grads, grads2, n, shift, vec, (double*)scratch);
+    return np;
+}
+
+extern "C" int32_t mst_grad_norm(const float* grads, const float* grads2, int64_t n, void* scratch, float* norm, mst_stream stream) {
+    if (!norm) return MST_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t np = gs_launch_sumsq(grads, grads2, n, scratch, s);
+    if (np < 0) return (int32_t)np;
+    hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(GS_THREADS), 0, s, (const double*)scratch, np, norm);
+    return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
+}
+
+extern "C" int32_t mst_grad_norms(const float* grads, const float* grads2, const int64_t* offsets, const int64_t* lengths,
+                                  int32_t count, float* norms, mst_stream stream) {
+    if (!grads || !offsets || !lengths || !norms || count <= 0 || ((uintptr_t)grads & 3) || ((uintptr_t)grads2 & 3)) return MST_ERR_ARG;
+    hipLaunchKernelGGL(grad_norms_kernel, dim3((unsigned)count), dim3(GS_THREADS), 0, (hipStream_t)stream, grads, grads2, offsets,
+                       lengths, norms);
+    return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
+}
+
+extern "C" int32_t mst_adam_step_guarded(float* params, float* grads, float* grads2, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                         float* state, float* guard, void* scratch, double lr0, double beta1, double beta2,
+                                         double eps, int32_t step_size, double gamma, double max_norm, int32_t skip_nonfinite,
+                                         int32_t zero_grad, mst_stream stream) {
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !state || !guard || n <= 0 || step_size <= 0 || max_norm != max_norm)
+        return MST_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t np = gs_launch_sumsq(grads, grads2, n, scratch, s);
+    if (np < 0) return (int32_t)np;
+    const int clip = max_norm > 0.0 && max_norm <= 3.4028234663852886e38;      // <= 0, +inf or beyond fp32: no clipping
+    hipLaunchKernelGGL(adam_prepare_guarded_kernel, dim3(1), dim3(GS_THREADS), 0, s, state, guard, (const double*)scratch, np, lr0,
+                       beta1, beta2, (int)step_size, gamma, clip ? (float)max_norm : 0.f, clip, (int)(skip_nonfinite != 0));
+    int64_t nb = (n + 1023) / 1024;
+    if (nb > 2048) nb = 2048;
+    hipLaunchKernelGGL(adam_guarded_kernel, dim3((unsigned)nb), dim3(256), 0, s, params, grads, grads2, exp_avg, exp_avg_sq, n,
+                       (const float*)state, (const float*)guard, (float)beta1, (float)beta2, (float)eps, (int)zero_grad);
+    return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
 }
 
 // ------------------------------------------------------------------ hard_output

@@ -105,6 +105,11 @@ _SIGS = {
                                   C.c_int32, C.c_double, C.c_int32, _P]),
     'mst_adam_step2': (C.c_int32, [_P, _P, _P, _P, _P, C.c_int64, _P, C.c_double, C.c_double, C.c_double, C.c_double,
                                    C.c_int32, C.c_double, C.c_int32, _P]),
+    'mst_grad_guard_scratch_bytes': (C.c_int64, [C.c_int64]),
+    'mst_grad_norm': (C.c_int32, [_P, _P, C.c_int64, _P, _P, _P]),
+    'mst_grad_norms': (C.c_int32, [_P, _P, _P, _P, C.c_int32, _P, _P]),
+    'mst_adam_step_guarded': (C.c_int32, [_P, _P, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double,
+                                          C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, _P]),
     'mst_hard_output': (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P]),
     'mst_clip_scatter': (C.c_int32, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _P, _P]),
     'mst_roll_slices': (C.c_int64, [C.c_int64]),

@@ -99,9 +99,11 @@ class SmallInputStager:
 class LossLog:
     """Packed loss tensors of the iterations since the last flush."""
 
-    def __init__(self, path, pbar, flush_every, health=None):
+    def __init__(self, path, pbar, flush_every, health=None, tolerate_nan=False, guard_stats=None):
         self.path, self.pbar, self.flush_every = path, pbar, flush_every
         self.health = health          # callable raising on a device-side failure (StyleTransferModel.check_device_status)
+        self.tolerate_nan = tolerate_nan      # a NaN loss is written as a row (the optimizer skips such a step) instead of asserted on
+        self.guard_stats = guard_stats        # callable returning FusedAdam.guard_stats() (or None): shown by the progress meter
         self.pending = []
 
     def add(self, iteration, packed):
@@ -118,10 +120,15 @@ class LossLog:
         rows = []
         for (iteration, _), v in zip(self.pending, values):
             leaf = dict(zip(_native.LOSS_KEYS, v.tolist()))
-            assert not math.isnan(leaf['total']), f'loss is NaN at iteration {iteration}'
+            assert self.tolerate_nan or not math.isnan(leaf['total']), f'loss is NaN at iteration {iteration}'
             has_u = not math.isnan(leaf['channels_loss_unpitched_total'])
-            rows.append(dict(iteration=iteration, **{k: ('' if math.isnan(x) else x) for k, x in leaf.items()}))
-            if self.pbar is not None:
+            row = dict(iteration=iteration, **{k: ('' if math.isnan(x) else x) for k, x in leaf.items()})
+            if math.isnan(leaf['total']):
+                row['total'] = 'nan'          # tolerated: the row says so, where an absent leaf is an empty cell
+            rows.append(row)
+            if self.pbar is not None and math.isnan(leaf['total']):
+                self.pbar.add(1)              # counted, but kept out of the meter's averages
+            elif self.pbar is not None:
                 self.pbar.add(1, total_loss=leaf['total'], pitched_loss=leaf['channels_loss_pitched_total'],
                               pitched_notes_loss=leaf['channels_loss_pitched_notes_loss'],
                               song_info_loss=leaf['song_info_loss_total'],
@@ -131,6 +138,15 @@ class LossLog:
                 if has_u:
                     self.pbar.update_values(1, unpitched_loss=leaf['channels_loss_unpitched_total'],
                                             unpitched_notes_loss=leaf['channels_loss_unpitched_notes_loss'])
+        stats = self.guard_stats() if self.guard_stats is not None and self.pbar is not None else None
+        if stats is not None:
+            # at the flush, where the loop synchronises anyway; the CSV keeps its columns.  Shown as they are (the last step's
+            # norm, the count of skipped steps), not momentum-averaged: their running sums start afresh
+            for k in ('grad_norm', 'skipped'):
+                self.pbar.values_sum.pop(k, None)
+                self.pbar.values_seen.pop(k, None)
+            self.pbar.update_values(1, grad_norm=stats['norm'] if math.isfinite(stats['norm']) else None,
+                                    skipped=float(stats['steps_skipped']))
         if self.path:
             self._append_rows(rows)
         self.pending = []
@@ -148,7 +164,8 @@ class LossLog:
 
 
 def train(model, inputs, n_iterations=5000, iter_size=2, training_info_path='training.csv', save_path='snapshots/',
-          save_interval=100, flush_every=20, progress=True, optimizer=None, fused=True, sparse_input=False):
+          save_interval=100, flush_every=20, progress=True, optimizer=None, fused=True, sparse_input=False,
+          max_grad_norm=None, skip_nonfinite=False, save_optimizer=False):
     """`inputs`: iterator of (filename, get_input(...)) tuples, e.g. iter_parallel(iter_inputs(...)).
     fused=True runs a loop body as ONE C-ABI call (StyleTransferModel.train_iteration: same arithmetic, same gradients, no
     autograd graph); fused=False is the reference's own sequence model(...) -> get_total_loss -> backward.
@@ -157,25 +174,33 @@ def train(model, inputs, n_iterations=5000, iter_size=2, training_info_path='tra
     kernel that builds the dense tensors on the device (mst_clip_scatter).  Same tensors bit for bit, hence the same losses.
     The prefetch thread runs ahead of the loop: when train() returns it has taken one or two songs more from `inputs` than
     the loop used, and it is told to stop and joined for up to 5 s — a daemon thread that is still blocked inside the
-    caller's iterator after that (a slow parse) ends with it."""
+    caller's iterator after that (a slow parse) ends with it.
+    max_grad_norm / skip_nonfinite configure the default FusedAdam's guard (global gradient-norm clipping, and skipping a step
+    whose gradient norm is inf / NaN — decided on the device, inside the optimizer step); with an `optimizer` of the caller's
+    they are refused: configure that optimizer instead.  With skip_nonfinite a NaN loss is logged as a row, not asserted on.
+    save_optimizer=True writes optimizer.state_dict() as `{iteration}.optim.pkl` beside every model snapshot."""
+    if optimizer is not None and (max_grad_norm is not None or skip_nonfinite):
+        raise ValueError('max_grad_norm / skip_nonfinite configure the default optimizer; with optimizer= set them on that optimizer')
     feeder = None
     if sparse_input:
         feeder = ParallelIterable(iter_sparse(inputs))
         inputs = iter(feeder)
     try:
         return _train_loop(model, inputs, n_iterations, iter_size, training_info_path, save_path, save_interval, flush_every,
-                           progress, optimizer, fused, sparse_input)
+                           progress, optimizer, fused, sparse_input, max_grad_norm, skip_nonfinite, save_optimizer)
     finally:
         if feeder is not None:
             feeder.stop(timeout=5.)
 
 
 def _train_loop(model, inputs, n_iterations, iter_size, training_info_path, save_path, save_interval, flush_every, progress,
-                optimizer, fused, sparse_input):
-    optimizer = optimizer or FusedAdam(model, lr=.01, step_size=200, gamma=.9)
+                optimizer, fused, sparse_input, max_grad_norm=None, skip_nonfinite=False, save_optimizer=False):
+    optimizer = optimizer or FusedAdam(model, lr=.01, step_size=200, gamma=.9, max_grad_norm=max_grad_norm,
+                                       skip_nonfinite=skip_nonfinite)
     optimizer.zero_grad()
     pbar = ProgressBar(n_iterations) if progress else None
-    log = LossLog(training_info_path, pbar, flush_every, health=getattr(model, 'check_device_status', None))
+    log = LossLog(training_info_path, pbar, flush_every, health=getattr(model, 'check_device_status', None),
+                  tolerate_nan=bool(getattr(optimizer, 'skip_nonfinite', False)), guard_stats=getattr(optimizer, 'guard_stats', None))
     stager = SmallInputStager(device) if sparse_input else None
     for iteration in range(n_iterations):
         if sparse_input:
@@ -213,6 +238,9 @@ def _train_loop(model, inputs, n_iterations, iter_size, training_info_path, save
             assert_dir(path)
             with open(path, 'wb') as f:
                 torch.save(model, f)
+            if save_optimizer:
+                with open(os.path.join(save_path, f'{iteration}.optim.pkl'), 'wb') as f:
+                    torch.save(optimizer.state_dict(), f)
     log.flush()
     return model
 
