@@ -285,6 +285,52 @@ int32_t mst_roll_count(const float* x, int64_t n_cells, int32_t nfeat, int32_t m
 int32_t mst_roll_compact(const float* x, int64_t n_cells, int32_t nfeat, int32_t mode, const int32_t* ws,
                          int64_t capacity, int32_t* cells, float* feats, mst_stream stream);
 
+/* ---- note metrics: how good are hard_output's decisions?  No reference counterpart: the reference has no validation, and
+ * get_total_loss (style/model.py:935-997) reports soft quantities only — its smooth F1 is computed on raw velocities, while the
+ * inference driver writes hard_output's decisions (style/model.py:818-832) to MIDI.
+ * pred, target: two rolls of n_groups x group_cells cells of nfeat (5 or 2) floats; a group is a run of consecutive cells — for
+ * the model's tensors one (clip, channel) of the pitched roll or one clip of the unpitched roll.  out: one record of
+ * MST_METRIC_WORDS doubles per group:
+ *   [0] cells in the group
+ *   [1] n_pred: cells with v_pred > .01f (hard_output's note decision; a NaN velocity is off, as in MST_ROLL_HARD)
+ *   [2] n_tgt:  cells with v_tgt > 0.f (the loss's mask)
+ *   [3] TP:     both
+ *   [4] of the TP cells, those whose three hard accidentals ((x[a] == max && x[a] > .1f) ? 1 : 0, mst_hard_output's operations)
+ *       equal the target's three accidentals as floats; 0 for nfeat == 2
+ *   [5] sum over the TP cells of fabsf(v_pred - v_tgt)
+ *   [6] sum over the TP cells of fabsf(d_pred - fminf(d_tgt, 6.f)) (get_duration_loss's clamp); a NaN duration on a matched
+ *       note makes it NaN
+ *   [7] 0
+ * Counts are exact integers held in doubles; [5] and [6] take the fp32 term, widen it and accumulate in double.
+ * The groups are cut into mst_roll_slices(group_cells) slices each; a workgroup owns one slice of one group, streams it from both
+ * tensors once and leaves a 32-byte partial in `scratch` (mst_roll_metrics_scratch_bytes, 8-byte aligned); a second launch adds a
+ * group's partials in a fixed order.  The number of partials depends on the arguments alone; no atomics, no workgroup waits for
+ * another: the same bits on every run.  Two launches per 65535 groups, enqueue-only on `stream` (no allocation, no host
+ * synchronisation, capturable as a single chain).  Every word of `out` and nothing beyond it is written; pred and target are
+ * read only and need float alignment only, each its own.
+ * MST_ERR_ARG: null pointer, nfeat outside {2, 5}, n_groups < 1, group_cells < 1 or >= 2^31, n_groups x slices >= 2^31, pred /
+ * target not 4-byte aligned, scratch / out not 8-byte aligned. */
+#define MST_METRIC_WORDS 8
+int64_t mst_roll_metrics_scratch_bytes(int64_t n_groups, int64_t group_cells);   /* <= 0 on bad arguments */
+int32_t mst_roll_metrics(const float* pred, const float* target, int64_t n_groups, int64_t group_cells,
+                         int32_t nfeat, void* scratch, double* out, mst_stream stream);
+
+/* ---- one evaluation iteration: mst_train_iteration without its backward half — the whole-model forward, get_total_loss with
+ * normalize = 1 against the inputs as targets, and the note metrics of the predictions.  No gradient is formed (there is no
+ * gparams argument), `params` is read only.  The small inputs and targets (mode, bpm, instr, used_instruments, bpm_target) sit
+ * in the workspace slots mst_train_iteration reads.  With mst_dims.clips = K: losses is K x MST_N_LOSSES (may be null), metrics
+ * K x (C + 2) records of MST_METRIC_WORDS doubles per clip: the C pitched channels ("pitched_pred" in the workspace against the
+ * borrowed `pitched`), one unpitched record (all zero when the plan has no percussion) and one song-info record:
+ *   [0] n_instruments                 [3] instruments with both
+ *   [1] instruments with logit > 0    [4] 1 if the first index of the largest mode logit is that of the largest mode target
+ *   [2] instruments with target > .5  [5] fabsf(bpm_pred - bpm_target)        [6..7] 0
+ * scratch: mst_eval_scratch_bytes(p) bytes of the caller's, 8-byte aligned (the plan's workspace layout is unchanged).  Three
+ * launches behind the loss: the two rolls' partials and one finishing launch for every record.  Enqueue-only on `stream`.
+ * A tiled plan (tile_rows > 0) gives MST_ERR_UNSUPPORTED. */
+int64_t mst_eval_scratch_bytes(const mst_plan* p);
+int32_t mst_eval_iteration(const mst_plan* p, const float* params, float* ws, const float* pitched,
+                           const float* unpitched, float* losses, double* metrics, void* scratch, mst_stream stream);
+
 /* ---- instrumentation (bench.py only; synchronises on HIP events, never used for training):
  * average duration of every launch step of a pass, with its algorithmic FLOPs and bytes.
  * kind: 0 gemm, 1 gather, 2 segment-reduce, 3/4 lstm fwd/bwd, 5/6 combine fwd/bwd, 7/8 melody notes, 9/10 applier notes,

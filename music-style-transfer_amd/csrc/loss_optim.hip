@@ -1091,3 +1091,187 @@ extern "C" int32_t mst_roll_compact(const float* x, int64_t n_cells, int32_t nfe
         hipLaunchKernelGGL(roll_emit_kernel<2>, dim3(nb), dim3(ROLL_THREADS), 0, s, x, n_cells, shift, (int)mode, ws, capacity, cells, feats);
     return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
 }
+
+// ------------------------------------------------------------------ note metrics (mst_roll_metrics, mst_eval_iteration)
+// How good are hard_output's decisions?  Prediction and target are streamed once, like roll_count_kernel streams one roll: a
+// workgroup owns one slice of ROLL_SLICE cells of ONE group (a run of consecutive cells: a channel of a clip), stages the slice
+// of both tensors into LDS with roll_stage (two images, 41 KB at five features; each tensor with the shift of its own group
+// base, so the two may be misaligned differently and an odd group_cells only changes every second group's shift) and leaves one
+// 32-byte partial: four counts and two double sums.  A second launch, one workgroup per group, adds the group's partials in a
+// fixed order.  No atomics, no workgroup waits for another, the number of partials depends on the arguments alone: the same
+// bits on every run.  The per-lane cell order is roll_count_kernel's (ROLL_CELL), the workgroup reduction grad_sumsq_kernel's.
+struct MetricPartial { int32_t n_pred, n_tgt, tp, acc; double vel, dur; };
+static_assert(sizeof(MetricPartial) == 32, "one 32-byte partial per slice");
+#define METRIC_MAX_GRID_Y 65535  // groups one launch takes in blockIdx.y; more groups are more launches of the same chain
+
+extern "C" int64_t mst_roll_metrics_scratch_bytes(int64_t n_groups, int64_t group_cells) {
+    const int64_t slices = mst_roll_slices(group_cells);
+    if (n_groups < 1 || slices < 1 || n_groups >= ((int64_t)1 << 31) || n_groups * slices >= ((int64_t)1 << 31)) return MST_ERR_ARG;
+    return n_groups * slices * (int64_t)sizeof(MetricPartial);
+}
+
+// group g = g0 + blockIdx.y is channel g % gpc of clip g / gpc; a clip's groups are consecutive, clips sit pred_cs / tgt_cs
+// floats apart (a plan's workspace slices against the caller's dense batch)
+template <int NFEAT>
+__global__ __launch_bounds__(ROLL_THREADS) void roll_metrics_kernel(const float* pred, const float* target, int64_t group_cells, int64_t g0,
+                                                                    int gpc, int64_t pred_cs, int64_t tgt_cs, MetricPartial* partials) {
+    __shared__ roll_f4 imgp4[ROLL_SLICE * NFEAT / 4 + 1];
+    __shared__ roll_f4 imgt4[ROLL_SLICE * NFEAT / 4 + 1];
+    __shared__ int redi[ROLL_WAVES][4];
+    __shared__ double redd[ROLL_WAVES][2];
+    const int64_t g = g0 + blockIdx.y;
+    const float* pg = pred + (g / gpc) * pred_cs + (g % gpc) * group_cells * NFEAT;
+    const float* tg = target + (g / gpc) * tgt_cs + (g % gpc) * group_cells * NFEAT;
+    const int shp = (int)(((uintptr_t)pg & 15) / 4), sht = (int)(((uintptr_t)tg & 15) / 4);
+    const int cells = roll_stage<NFEAT>(pg, group_cells, shp, imgp4);
+    roll_stage<NFEAT>(tg, group_cells, sht, imgt4);
+    const float* ip = reinterpret_cast<const float*>(imgp4) + shp;
+    const float* it = reinterpret_cast<const float*>(imgt4) + sht;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int cnt[4] = {0, 0, 0, 0};
+    double vel = 0.0, dur = 0.0;
+#pragma unroll
+    for (int j = 0; j < ROLL_PER_LANE; ++j) {
+        const int c = ROLL_CELL(wave, j, lane);
+        if (c >= cells) continue;
+        const float* p = ip + c * NFEAT;
+        const float* t = it + c * NFEAT;
+        float hard[NFEAT];
+        const bool on = roll_record<NFEAT>(p, MST_ROLL_HARD, hard);      // hard_output's decisions (a NaN velocity is off)
+        const bool want = t[1] > 0.f;                                    // the loss's mask
+        cnt[0] += on;
+        cnt[1] += want;
+        if (on && want) {
+            ++cnt[2];
+            if (NFEAT > 2) {
+                bool same = true;
+#pragma unroll
+                for (int a = 2; a < NFEAT; ++a) same = same && hard[a] == t[a];
+                cnt[3] += same;
+            }
+            vel += (double)fabsf(p[1] - t[1]);
+            dur += (double)fabsf(p[0] - fminf(t[0], 6.f));               // get_duration_loss's clamp
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) cnt[k] += __shfl_xor(cnt[k], o);
+    }
+    vel = wave_sum_d(vel);
+    dur = wave_sum_d(dur);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) redi[wave][k] = cnt[k];
+        redd[wave][0] = vel;
+        redd[wave][1] = dur;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        MetricPartial m = {0, 0, 0, 0, 0.0, 0.0};
+        for (int w = 0; w < ROLL_WAVES; ++w) {
+            m.n_pred += redi[w][0]; m.n_tgt += redi[w][1]; m.tp += redi[w][2]; m.acc += redi[w][3];
+            m.vel += redd[w][0]; m.dur += redd[w][1];
+        }
+        partials[g * gridDim.x + blockIdx.x] = m;
+    }
+}
+
+// The whole workgroup: a group's partials in a fixed order (per-lane chains over q = lane, lane + 256, ..., a wave shuffle sum,
+// the four wave sums in wave order) into one record.  Counts travel as doubles: integers below 2^53 are exact in any order.
+__device__ __forceinline__ void metrics_finish_group(const MetricPartial* part, int64_t np, int64_t cells, double* rec) {
+    __shared__ double red[6][ROLL_WAVES];
+    double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int64_t q = threadIdx.x; q < np; q += ROLL_THREADS) {
+        const MetricPartial m = part[q];
+        v[0] += (double)m.n_pred; v[1] += (double)m.n_tgt; v[2] += (double)m.tp; v[3] += (double)m.acc;
+        v[4] += m.vel; v[5] += m.dur;
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        v[k] = wave_sum_d(v[k]);
+        if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        rec[0] = (double)cells;
+        for (int k = 0; k < 6; ++k) {
+            double total = 0.0;
+            for (int w = 0; w < ROLL_WAVES; ++w) total += red[k][w];
+            rec[1 + k] = total;
+        }
+        rec[7] = 0.0;
+    }
+}
+
+__global__ __launch_bounds__(ROLL_THREADS) void roll_metrics_finish_kernel(const MetricPartial* partials, int64_t slices, int64_t cells,
+                                                                           double* out) {
+    metrics_finish_group(partials + (int64_t)blockIdx.x * slices, slices, cells, out + (int64_t)blockIdx.x * MST_METRIC_WORDS);
+}
+
+// finishing launch of an evaluation iteration: workgroup b writes record b % (C + 2) of clip b / (C + 2) — a pitched channel,
+// the unpitched roll (all zero without percussion) or the song-info record
+__global__ __launch_bounds__(ROLL_THREADS) void eval_metrics_finish_kernel(EvalMetricsArgs a) {
+    const int per = a.C + 2;
+    const int64_t k = blockIdx.x / per;
+    const int r = blockIdx.x % per;
+    double* rec = a.out + (int64_t)blockIdx.x * MST_METRIC_WORDS;
+    if (r < a.C) {
+        metrics_finish_group((const MetricPartial*)a.part_p + (k * a.C + r) * a.slices_p, a.slices_p, a.cells_p, rec);
+    } else if (r == a.C) {
+        if (a.part_u) metrics_finish_group((const MetricPartial*)a.part_u + k * a.slices_u, a.slices_u, a.cells_u, rec);
+        else if (threadIdx.x < MST_METRIC_WORDS) rec[threadIdx.x] = 0.0;
+    } else if (threadIdx.x == 0) {
+        const float* il = a.il + k * a.ws_stride; const float* it = a.it + k * a.ws_stride;
+        const float* ml = a.mlg + k * a.ws_stride; const float* mt = a.mt + k * a.ws_stride;
+        int n_pred = 0, n_tgt = 0, both = 0;
+        for (int j = 0; j < a.ni; ++j) {
+            const bool on = il[j] > 0.f, want = it[j] > .5f;
+            n_pred += on; n_tgt += want; both += on && want;
+        }
+        rec[0] = (double)a.ni; rec[1] = (double)n_pred; rec[2] = (double)n_tgt; rec[3] = (double)both;
+        rec[4] = (ml[1] > ml[0]) == (mt[1] > mt[0]) ? 1.0 : 0.0;       // first index of the largest of two
+        rec[5] = (double)fabsf(a.bp[k * a.ws_stride] - a.bt[k * a.ws_stride]);
+        rec[6] = rec[7] = 0.0;
+    }
+}
+
+static bool roll_metrics_args_ok(const float* pred, const float* target, int64_t n_groups, int64_t group_cells, int32_t nfeat,
+                                 const void* scratch) {
+    return pred && target && scratch && (nfeat == 5 || nfeat == 2) && mst_roll_metrics_scratch_bytes(n_groups, group_cells) > 0 &&
+           !((uintptr_t)pred & 3) && !((uintptr_t)target & 3) && !((uintptr_t)scratch & 7);
+}
+
+int launch_roll_metrics(const float* pred, const float* target, int64_t n_groups, int64_t group_cells, int nfeat, int gpc,
+                        int64_t pred_cs, int64_t tgt_cs, void* scratch, hipStream_t s) {
+    if (!roll_metrics_args_ok(pred, target, n_groups, group_cells, nfeat, scratch) || gpc < 1 || ((pred_cs | tgt_cs) < 0)) return MST_ERR_ARG;
+    const unsigned nb = (unsigned)mst_roll_slices(group_cells);
+    for (int64_t g0 = 0; g0 < n_groups; g0 += METRIC_MAX_GRID_Y) {
+        const unsigned ny = (unsigned)(n_groups - g0 < METRIC_MAX_GRID_Y ? n_groups - g0 : METRIC_MAX_GRID_Y);
+        if (nfeat == 5)
+            hipLaunchKernelGGL(roll_metrics_kernel<5>, dim3(nb, ny), dim3(ROLL_THREADS), 0, s, pred, target, group_cells, g0, gpc, pred_cs,
+                               tgt_cs, (MetricPartial*)scratch);
+        else
+            hipLaunchKernelGGL(roll_metrics_kernel<2>, dim3(nb, ny), dim3(ROLL_THREADS), 0, s, pred, target, group_cells, g0, gpc, pred_cs,
+                               tgt_cs, (MetricPartial*)scratch);
+    }
+    return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
+}
+
+int launch_eval_metrics_finish(const EvalMetricsArgs& a, int clips, hipStream_t s) {
+    hipLaunchKernelGGL(eval_metrics_finish_kernel, dim3((unsigned)(clips * (a.C + 2))), dim3(ROLL_THREADS), 0, s, a);
+    return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
+}
+
+extern "C" int32_t mst_roll_metrics(const float* pred, const float* target, int64_t n_groups, int64_t group_cells, int32_t nfeat,
+                                    void* scratch, double* out, mst_stream stream) {
+    if (!out || ((uintptr_t)out & 7)) return MST_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    // one clip of n_groups consecutive groups
+    const int gpc = (int)(n_groups < 0x7fffffff ? n_groups : 0x7fffffff);
+    const int e = launch_roll_metrics(pred, target, n_groups, group_cells, nfeat, gpc, 0, 0, scratch, s);
+    if (e) return e;
+    hipLaunchKernelGGL(roll_metrics_finish_kernel, dim3((unsigned)n_groups), dim3(ROLL_THREADS), 0, s, (const MetricPartial*)scratch,
+                       mst_roll_slices(group_cells), group_cells, out);
+    return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
+}

@@ -397,6 +397,20 @@ int loss_bwd_batched(const float* pp, const float* pt, int64_t np, const float* 
                      const float* saved, const float* gl, float* gp, float* gu, float* gi, float* gm, float* gb, LossBatch lb,
                      hipStream_t s, float info_scale = 1.f /* 0 on the non-root ranks of a tiled plan: the song-info gradients are
                                                               replicated, only one rank may contribute them to the summed gradient */);
+// note metrics of an evaluation iteration (loss_optim.hip): per-slice partials of `n_groups` groups of `group_cells` cells —
+// group g is channel g % gpc of clip g / gpc, clips pred_cs / tgt_cs floats apart — into `scratch` (32 bytes per slice and group),
+// and the finishing launch that writes a clip's C pitched records, its unpitched record and its song-info record
+int launch_roll_metrics(const float* pred, const float* target, int64_t n_groups, int64_t group_cells, int nfeat, int gpc,
+                        int64_t pred_cs, int64_t tgt_cs, void* scratch, hipStream_t s);
+struct EvalMetricsArgs {
+    const void* part_p; int64_t slices_p, cells_p;
+    const void* part_u; int64_t slices_u, cells_u;          // part_u null: no percussion, the record is all zero
+    int32_t C, ni;
+    const float *il, *it, *mlg, *mt, *bp, *bt;              // clip 0's song-info predictions and targets
+    int64_t ws_stride;                                      // floats between two clips' copies of them
+    double* out;                                            // clips x (C + 2) records of MST_METRIC_WORDS doubles
+};
+int launch_eval_metrics_finish(const EvalMetricsArgs& a, int clips, hipStream_t s);
 bool rowlin_supported(int kin, int nout);
 int launch_rowlin_fwd(const RowLinDesc* dev, const RowLinDesc& host, int count, Bases b, hipStream_t s);
 int launch_rowlin_bwd(const RowLinDesc* dev, const RowLinDesc& host, int count, Bases b, hipStream_t s);

@@ -2063,6 +2063,54 @@ extern "C" int32_t mst_train_iteration(const mst_plan* p, const float* params, f
     return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
 }
 
+// ------------------------------------------------------------------------------------------ evaluation
+// mst_train_iteration without its backward half, plus the note metrics.  There is no zero launch here, so the forward runs as
+// mst_forward runs it: the multi-workgroup LSTM's transpose step clears the exchange tags itself.
+static int64_t eval_slices(const mst_plan* p, bool pitched) {
+    return mst_roll_slices(pitched ? (int64_t)p->Q() * NF * NPN : (int64_t)p->Q() * NF * NUN);
+}
+
+extern "C" int64_t mst_eval_scratch_bytes(const mst_plan* p) {
+    if (!p) return MST_ERR_ARG;
+    if (p->tiled()) return MST_ERR_UNSUPPORTED;
+    return 32 * (int64_t)p->K() * ((int64_t)p->d.C * eval_slices(p, true) + (p->d.has_unpitched ? eval_slices(p, false) : 0));
+}
+
+extern "C" int32_t mst_eval_iteration(const mst_plan* p, const float* params, float* ws, const float* pitched,
+                                      const float* unpitched, float* losses, double* metrics, void* scratch, mst_stream stream) {
+    if (!p || !params || !ws || !pitched || !metrics || !scratch || ((uintptr_t)metrics & 7) || ((uintptr_t)scratch & 7)) return MST_ERR_ARG;
+    if (p->tiled()) return MST_ERR_UNSUPPORTED;
+    if (p->d.has_unpitched && !unpitched) return MST_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    int e = run_pass(p, p->list(MST_STAGE_ALL, 0), MST_STAGE_ALL, make_bases(p, params, nullptr, ws, pitched, unpitched), st);
+    if (e) return e;
+    const bool U = p->d.has_unpitched != 0;
+    const int K = p->K(), C = p->d.C;
+    auto at = [&](const char* n) { return p->named.at(n).off; };
+    const int64_t np = (int64_t)p->P() * NF * NPN, nu = U ? (int64_t)p->Q() * NF * NUN : 0;
+    float* lscratch = ws + 2 * (int64_t)K * p->act_top + p->loss_scratch;
+    const LossBatch lb = {K, p->act_top, p->act_top, p->tmp_top, p->ext0_stride(), p->ext1_stride()};
+    e = loss_fwd_batched(ws + at("pitched_pred"), pitched, np, U ? ws + at("unpitched_pred") : nullptr, U ? unpitched : nullptr,
+                         nu, ws + at("instruments_pred"), ws + at("used_instruments"), p->z.NI, ws + at("mode_pred"),
+                         ws + at("mode"), ws + at("bpm_pred"), ws + at("bpm_target"), 1, ws + p->t_losses.off,
+                         ws + p->t_saved.off, lscratch, lb, st, ws + p->t_gl.off, losses);
+    if (e) return e;
+    EvalMetricsArgs a{};
+    a.part_p = scratch; a.slices_p = eval_slices(p, true); a.cells_p = np / C;
+    e = launch_roll_metrics(ws + at("pitched_pred"), pitched, (int64_t)K * C, a.cells_p, NPF, C, p->act_top, p->ext0_stride(), scratch, st);
+    if (e) return e;
+    if (U) {
+        void* su = (char*)scratch + 32 * (int64_t)K * C * a.slices_p;
+        a.part_u = su; a.slices_u = eval_slices(p, false); a.cells_u = nu;
+        e = launch_roll_metrics(ws + at("unpitched_pred"), unpitched, K, nu, NUF, 1, p->act_top, p->ext1_stride(), su, st);
+        if (e) return e;
+    }
+    a.C = C; a.ni = p->z.NI;
+    a.il = ws + at("instruments_pred"); a.it = ws + at("used_instruments"); a.mlg = ws + at("mode_pred"); a.mt = ws + at("mode");
+    a.bp = ws + at("bpm_pred"); a.bt = ws + at("bpm_target"); a.ws_stride = p->act_top; a.out = metrics;
+    return launch_eval_metrics_finish(a, K, st);
+}
+
 
 // ------------------------------------------------------------------------------------------ tiled plans
 // One train iteration (train-model.py:113-126) of ONE long clip whose bars are tiled over several ranks (BASELINE.json

@@ -45,6 +45,7 @@ class PlanOptions(C.Structure):
 
 DEV_LSTM_TIMEOUT = 1        # mst_amd.h MST_DEV_LSTM_TIMEOUT
 ROLL_NONZERO, ROLL_HARD = 0, 1      # mst_amd.h MST_ROLL_*: record modes of mst_roll_count / mst_roll_compact
+METRIC_WORDS = 8                    # mst_amd.h MST_METRIC_WORDS: doubles per record of mst_roll_metrics / mst_eval_iteration
 
 
 def describe_status(word):
@@ -115,6 +116,10 @@ _SIGS = {
     'mst_roll_slices': (C.c_int64, [C.c_int64]),
     'mst_roll_count': (C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
     'mst_roll_compact': (C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P]),
+    'mst_roll_metrics_scratch_bytes': (C.c_int64, [C.c_int64, C.c_int64]),
+    'mst_roll_metrics': (C.c_int32, [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P]),
+    'mst_eval_scratch_bytes': (C.c_int64, [_P]),
+    'mst_eval_iteration': (C.c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'mst_plan_step_count': (C.c_int32, [_P, C.c_int32, C.c_int32]),
     'mst_plan_step_info': (C.c_int32, [_P, C.c_int32, C.c_int32, _P]),
     'mst_plan_step_carried': (C.c_int32, [_P, C.c_int32, C.c_int32, _P]),
@@ -208,6 +213,20 @@ class Native:
         addr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()
         check(self.lib.mst_roll_compact(addr(x), int(n_cells), int(nfeat), int(mode), addr(ws), int(capacity), addr(cells), addr(feats),
                                         stream), 'mst_roll_compact')
+
+    def roll_metrics_scratch_bytes(self, n_groups, group_cells):
+        n = self.lib.mst_roll_metrics_scratch_bytes(int(n_groups), int(group_cells))
+        if n <= 0:
+            raise MstError(f'mst_roll_metrics_scratch_bytes({n_groups}, {group_cells}): bad arguments')
+        return n
+
+    def roll_metrics(self, pred, target, n_groups, group_cells, nfeat, scratch, out, stream=None):
+        """mst_roll_metrics: one record of METRIC_WORDS float64 per group of `group_cells` consecutive cells into `out`, from the
+        rolls `pred` and `target` (n_groups x group_cells x nfeat floats each).  `scratch`: roll_metrics_scratch_bytes bytes,
+        8-byte aligned.  Tensors on one device or raw addresses.  Enqueue-only."""
+        addr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()
+        check(self.lib.mst_roll_metrics(addr(pred), addr(target), int(n_groups), int(group_cells), int(nfeat), addr(scratch), addr(out),
+                                        stream), 'mst_roll_metrics')
 
     def plan(self, dims, device):
         opts = options_from_env()
@@ -407,6 +426,25 @@ class Plan:
         check(self.lib.mst_train_iteration(self.handle, ptr(params), ptr(gparams), ptr(self._touch(ws)),
                                            ptr(pitched), ptr(unpitched), ptr(losses), current_stream(self.device)),
               'mst_train_iteration')
+
+    def eval_scratch(self):
+        """The partials buffer of eval_iteration, allocated once per plan."""
+        if getattr(self, '_eval_scratch', None) is None:
+            n = self.lib.mst_eval_scratch_bytes(self.handle)
+            if n <= 0:
+                check(int(n) or -1, 'mst_eval_scratch_bytes')
+            self._eval_scratch = torch.zeros(n // 8, dtype=torch.float64, device=self.device)
+        return self._eval_scratch
+
+    def eval_iteration(self, params, pitched, unpitched, losses, metrics, ws=None):
+        """mst_eval_iteration: forward, loss (normalize = 1, the inputs as targets) and note metrics, no backward.  `losses`:
+        clips x N_LOSSES float32 (or None), `metrics`: clips x (C + 2) x METRIC_WORDS float64.  Enqueue-only."""
+        if metrics.dtype != torch.float64 or not metrics.is_contiguous() or \
+                metrics.numel() != self.clips * (self.dims.C + 2) * METRIC_WORDS:
+            raise MstError('eval_iteration: metrics must be a contiguous float64 tensor of clips x (C + 2) x 8')
+        check(self.lib.mst_eval_iteration(self.handle, ptr(params), ptr(self._touch(ws)), ptr(pitched), ptr(unpitched), ptr(losses),
+                                          metrics.data_ptr(), self.eval_scratch().data_ptr(), current_stream(self.device)),
+              'mst_eval_iteration')
 
 
 _native = None

@@ -448,6 +448,46 @@ class StyleTransferModel(nn.Module):
             self._publish_grads()
         return row
 
+    def eval_iteration(self, mode, bpm, pitched_channels, instruments_features, unpitched_channels, used_instruments, bpm_target):
+        """One held-out evaluation of a song: train_iteration's forward and get_total_loss(normalize=True) with the inputs as
+        targets, no backward, plus the note metrics of hard_output's decisions on the predictions — ONE C-ABI call
+        (mst_eval_iteration).  The note tensors may be dense tensors or SparseRolls, exactly as for train_iteration.  Returns a
+        style.metrics.EvalResult: `.losses` (the 15 leaves, key order style._native.LOSS_KEYS) and `.metrics` ((C + 2) x 8
+        float64: the pitched channels, the unpitched roll — all zero without percussion — and the song info), both on the
+        device; nothing is read back.  No reference counterpart: the reference has no validation.
+
+        It runs on the current stream, behind whatever train_iteration has enqueued on its lanes (their bookkeeping is left
+        alone), in a workspace and static note buffers of its own per plan: it touches no lane's workspace, no gradient
+        buffer and not the lane counter, so the training it sits between is the same bits with or without it."""
+        from style.metrics import EvalResult
+        anchor = self._anchor()
+        dev = anchor.device
+        note = lambda t: t if t is None or isinstance(t, SparseRoll) else _f32c(t, dev)
+        pitched, unpitched = note(pitched_channels), note(unpitched_channels)
+        new_buf = lambda t: None if t is None else torch.empty(tuple(t.shape), dtype=torch.float32, device=dev)
+        _, C, R, T = pitched.shape[:4]
+        plan = self._plan(C, R, T, unpitched is not None, dev)
+        st = plan.__dict__.get('_eval_state')
+        if st is None:
+            st = plan.__dict__['_eval_state'] = dict(ws=plan.new_ws(), pitched=new_buf(pitched), unpitched=new_buf(unpitched), records={})
+        ws = st['ws']
+        self.join_lanes_keep()
+        srcs = [_f32c(mode, dev).reshape(-1), _f32c(bpm, dev).reshape(-1), _f32c(instruments_features, dev).reshape(-1),
+                _f32c(used_instruments, dev).reshape(-1),
+                torch.as_tensor(float(bpm_target), dtype=torch.float32).reshape(1).to(dev, non_blocking=True)]
+        dsts = [plan.view(n, ws=ws) for n in ('mode', 'bpm', 'instr', 'used_instruments', 'bpm_target')]
+        for t, buf in ((pitched, st['pitched']), (unpitched, st['unpitched'])):
+            if torch.is_tensor(t):
+                srcs.append(t.reshape(-1)); dsts.append(buf.reshape(-1))
+        torch._foreach_copy_(dsts, srcs)
+        for t, buf in ((pitched, st['pitched']), (unpitched, st['unpitched'])):
+            if isinstance(t, SparseRoll):
+                _scatter_records(t, buf, st['records'], dev)
+        losses = torch.empty(_native.N_LOSSES, dtype=torch.float32, device=dev)
+        metrics = torch.empty(C + 2, _native.METRIC_WORDS, dtype=torch.float64, device=dev)
+        plan.eval_iteration(self._flat, st['pitched'], st['unpitched'], losses, metrics, ws=ws)
+        return EvalResult(losses, metrics)
+
     def static_inputs(self, C, R, T, unpitched=True, lane=0):
         """The note-tensor buffers a captured train_iteration of this shape reads (created on first use by train_iteration): a
         loader that writes its H2D copies straight into them saves the per-iteration device copy."""

@@ -25,6 +25,7 @@ from style.data import (iter_inputs, instrument_size, n_instruments, included_in
 from style.model import (device, get_total_loss, PitchedChannelsEncoder, UnpitchedChannelsEncoder, PitchedRhythmEncoder,
                          UnpitchedRhythmEncoder, StyleEncoder, MelodyEncoder, SongInfoModel, PitchedStyleApplier,
                          UnpitchedStyleApplier, StyleTransferModel)
+from style.metrics import (NoteMetrics, SongInfoMetrics, append_validation_rows, nanmean_leaves, validation_row, WORDS)
 from style.optim import FusedAdam
 from style.utils.misc import ProgressBar, assert_dir
 from style.utils.parallel import iter_parallel, ParallelIterable
@@ -163,9 +164,48 @@ class LossLog:
             out.writerows([row[k] for k in CSV_FIELDS] for row in rows)
 
 
+def evaluate(model, inputs, n_clips, sparse_input=False):
+    """One held-out evaluation round: the next `n_clips` songs of `inputs` (items as `train` takes them) through
+    StyleTransferModel.eval_iteration — forward, loss and note metrics, no backward, no gradient, no optimizer.  The songs
+    are cut to `800 // C` bars and silence is treated as in the training loop: a song without pitched notes is skipped, not
+    counted; silent percussion is dropped.  sparse_input=True uploads the note tensors as note records.  Everything stays on
+    the device until ONE copy at the end.  Returns dict(clips, losses, pitched, unpitched, song_info): the loss leaves averaged
+    over the clips (a numpy array in style._native.LOSS_KEYS order; the unpitched leaves over the clips with percussion) and
+    the records summed over channels and clips (style.metrics.NoteMetrics / SongInfoMetrics, on the host), i.e.
+    micro-averages.  Fewer than `n_clips` clips are evaluated when `inputs` runs out."""
+    rows = []
+    while len(rows) < n_clips:
+        try:
+            input = next(inputs)
+        except StopIteration:
+            break
+        if sparse_input:
+            clip = prepare_input_sparse(input, 800 // input[1][1].shape[0]).drop_silent()
+            if clip is None:
+                continue
+            mode, bpm, pitched, features, unpitched = clip
+            bpm_target = clip.bpm_target
+        else:
+            input, max_n_bars = drop_silent(input)
+            if input is None:
+                continue
+            mode, bpm, pitched, features, unpitched = prepare_input(input, max_n_bars)
+            bpm_target = input[1][0]['bpm']
+        used = get_used_instruments(features, unpitched)
+        res = model.eval_iteration(mode, bpm, pitched, features, unpitched, used, bpm_target)
+        # a song's (C + 2) records as three: the pitched channels summed, the unpitched roll, the song info
+        rows.append(torch.cat([res.losses.double(), res.metrics[:-2].sum(0), res.metrics[-2], res.metrics[-1]]))
+    n = len(rows)
+    host = torch.stack(rows).cpu() if n else torch.zeros(0, _native.N_LOSSES + 3 * WORDS, dtype=torch.float64)     # the one D2H copy
+    records = host[:, _native.N_LOSSES:].reshape(n, 3, WORDS)
+    return dict(clips=n, losses=nanmean_leaves(host[:, :_native.N_LOSSES].numpy()), pitched=NoteMetrics(records[:, 0]).sum(),
+                unpitched=NoteMetrics(records[:, 1]).sum(), song_info=SongInfoMetrics.from_device(records[:, 2]).sum())
+
+
 def train(model, inputs, n_iterations=5000, iter_size=2, training_info_path='training.csv', save_path='snapshots/',
           save_interval=100, flush_every=20, progress=True, optimizer=None, fused=True, sparse_input=False,
-          max_grad_norm=None, skip_nonfinite=False, save_optimizer=False):
+          max_grad_norm=None, skip_nonfinite=False, save_optimizer=False, eval_inputs=None, eval_every=0, eval_clips=8,
+          eval_info_path='validation.csv'):
     """`inputs`: iterator of (filename, get_input(...)) tuples, e.g. iter_parallel(iter_inputs(...)).
     fused=True runs a loop body as ONE C-ABI call (StyleTransferModel.train_iteration: same arithmetic, same gradients, no
     autograd graph); fused=False is the reference's own sequence model(...) -> get_total_loss -> backward.
@@ -178,7 +218,12 @@ def train(model, inputs, n_iterations=5000, iter_size=2, training_info_path='tra
     max_grad_norm / skip_nonfinite configure the default FusedAdam's guard (global gradient-norm clipping, and skipping a step
     whose gradient norm is inf / NaN — decided on the device, inside the optimizer step); with an `optimizer` of the caller's
     they are refused: configure that optimizer instead.  With skip_nonfinite a NaN loss is logged as a row, not asserted on.
-    save_optimizer=True writes optimizer.state_dict() as `{iteration}.optim.pkl` beside every model snapshot."""
+    save_optimizer=True writes optimizer.state_dict() as `{iteration}.optim.pkl` beside every model snapshot.
+    eval_inputs (an iterator of held-out songs, items as `inputs`) with eval_every = N > 0 runs one `evaluate` round of
+    `eval_clips` songs after every N-th iteration and appends a row to `eval_info_path` (style.metrics.VALIDATION_FIELDS: the
+    iteration, the clip count, the averaged loss leaves and the note / song-info metrics of hard_output's decisions); the
+    progress meter shows `val_f1`.  Evaluation forms no gradient and leaves the training bits alone; with eval_inputs=None the
+    loop is what it is without this argument."""
     if optimizer is not None and (max_grad_norm is not None or skip_nonfinite):
         raise ValueError('max_grad_norm / skip_nonfinite configure the default optimizer; with optimizer= set them on that optimizer')
     feeder = None
@@ -187,14 +232,16 @@ def train(model, inputs, n_iterations=5000, iter_size=2, training_info_path='tra
         inputs = iter(feeder)
     try:
         return _train_loop(model, inputs, n_iterations, iter_size, training_info_path, save_path, save_interval, flush_every,
-                           progress, optimizer, fused, sparse_input, max_grad_norm, skip_nonfinite, save_optimizer)
+                           progress, optimizer, fused, sparse_input, max_grad_norm, skip_nonfinite, save_optimizer,
+                           eval_inputs if eval_every and eval_every > 0 else None, eval_every, eval_clips, eval_info_path)
     finally:
         if feeder is not None:
             feeder.stop(timeout=5.)
 
 
 def _train_loop(model, inputs, n_iterations, iter_size, training_info_path, save_path, save_interval, flush_every, progress,
-                optimizer, fused, sparse_input, max_grad_norm=None, skip_nonfinite=False, save_optimizer=False):
+                optimizer, fused, sparse_input, max_grad_norm=None, skip_nonfinite=False, save_optimizer=False,
+                eval_inputs=None, eval_every=0, eval_clips=8, eval_info_path='validation.csv'):
     optimizer = optimizer or FusedAdam(model, lr=.01, step_size=200, gamma=.9, max_grad_norm=max_grad_norm,
                                        skip_nonfinite=skip_nonfinite)
     optimizer.zero_grad()
@@ -232,6 +279,15 @@ def _train_loop(model, inputs, n_iterations, iter_size, training_info_path, save
         log.add(iteration, packed)
         if (iteration + 1) % iter_size == 0:
             optimizer.step()                      # Adam + StepLR + zero_grad in one launch
+        if eval_inputs is not None and (iteration + 1) % eval_every == 0:
+            result = evaluate(model, eval_inputs, eval_clips, sparse_input=sparse_input)
+            if eval_info_path:
+                append_validation_rows(eval_info_path, [validation_row(iteration, result['clips'], result['losses'], result['pitched'],
+                                                                       result['unpitched'], result['song_info'])])
+            if pbar is not None and not math.isnan(result['pitched'].f1):
+                for k in (pbar.values_sum, pbar.values_seen):       # shown as it is (the last round's), not momentum-averaged
+                    k.pop('val_f1', None)
+                pbar.update_values(1, val_f1=result['pitched'].f1)
         if iteration % save_interval == 0 and save_path:
             log.flush()
             path = os.path.join(save_path, f'{iteration}.pkl')
@@ -245,13 +301,27 @@ def _train_loop(model, inputs, n_iterations, iter_size, training_info_path, save
     return model
 
 
-def main(data_path='data/Lakh MIDI Dataset/clean_midi/', **kwargs):
+def split_eval_files(files, n_eval_files):
+    """(training files, held-out files): the files sorted, the last `n_eval_files` of them held out."""
+    files = sorted(files)
+    n = max(0, min(int(n_eval_files), len(files)))
+    return files[:len(files) - n], files[len(files) - n:]
+
+
+def main(data_path='data/Lakh MIDI Dataset/clean_midi/', n_eval_files=0, **kwargs):
+    """n_eval_files > 0 holds the last that many of the sorted files out of the training list and cycles them as the
+    `eval_inputs` of `train` (give eval_every as well)."""
     from style.utils.misc import iter_all_files
     print(f'Using {device}')
     print('Listing data files')
     files = list(iter_all_files(data_path, '**/*.mid'))
+    held_out = []
+    if n_eval_files:
+        files, held_out = split_eval_files(files, n_eval_files)
     print('Creating model')
     model = build_model()
     print('Training')
     inputs = iter_parallel(iter_inputs(files, included_instruments, shuffle=True, looped=True))
+    if held_out:
+        kwargs['eval_inputs'] = iter_parallel(iter_inputs(held_out, included_instruments, shuffle=False, looped=True))
     return train(model, inputs, **kwargs)
