@@ -13,6 +13,7 @@
 #include "mst_common.h"
 
 #define LSTM_ZS 8192        // floats of LDS holding staged per-step operands in the register flavours
+#define LSTM_MCH 32         // steps whose streamed operands the multi-workgroup backward stages in LDS at once
 __device__ __forceinline__ float sigm(float x) { return MST_FAST_RCP(1.f + MST_FAST_EXP(-x)); }
 __device__ __forceinline__ float tanh_fast(float x) { return 2.f * sigm(2.f * x) - 1.f; }
 __device__ __forceinline__ float wsum(float v) {
@@ -20,6 +21,9 @@ __device__ __forceinline__ float wsum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
+
+typedef float lstm_f4 __attribute__((ext_vector_type(4)));
+typedef float lstm_f4u __attribute__((ext_vector_type(4), aligned(4)));       // a 16-byte load from a 4-byte aligned address
 
 // REG (H <= 64) launches at most 256 lanes, so it may use the whole register file of one wave per SIMD
 template <bool REG>
@@ -39,12 +43,15 @@ __global__ __launch_bounds__(REG ? 256 : 1024) void lstm_fwd_kernel(const LstmDe
     float* ws = b.p[SP_WS];
     float* tmp = b.p[SP_TMP];
     float w[REG ? 64 : 1];
+    // REG: the lane's W_hh row as sixteen 16-byte loads (4-byte aligned: any H, any offset) instead of 64 scalar ones, each of which
+    // touched a cache line per lane.  A load starts at flat element tid * H + k, clamped so that it ends inside W_hh: a group
+    // that runs over the end of the row reads into the next row (dropped below), and only at the end of the matrix does the clamp
+    // shift a lane's group by `sh` elements (undone below).  No branches, all sixteen in flight.
+    lstm_f4u wv[REG ? 16 : 1];
+    const int wlast = max(G * H - 4, 0);         // H >= 1: the matrix holds at least four floats
     if (REG && tid < G) {
 #pragma unroll
-        for (int k = 0; k < 64; ++k) {       // unconditional (clamped) loads: all 64 in flight, no branches
-            const float v = whh[(int64_t)tid * H + min(k, H - 1)];
-            w[k] = k < H ? v : 0.f;
-        }
+        for (int k4 = 0; k4 < 16; ++k4) wv[k4] = *reinterpret_cast<const lstm_f4u*>(whh + min(tid * H + 4 * k4, wlast));
     }
     float bias[4] = {0.f, 0.f, 0.f, 0.f}, zq[4] = {0.f, 0.f, 0.f, 0.f};
     const int s0 = d.reverse ? d.S - 1 : 0;
@@ -55,9 +62,48 @@ __global__ __launch_bounds__(REG ? 256 : 1024) void lstm_fwd_kernel(const LstmDe
             if (!REG) zq[q] = zx[((int64_t)bi * d.S + s0) * G + q * H + tid];
         }
     }
-    if (REG) {               // landed before the loop: the step loop then holds no load wait that would also drain its stores
+    // REG: the zx rows of the zchunk steps from `step` on, into LDS
+    auto fetch = [&](const int step) {
+        const int cnt = min(zchunk, d.S - step);
+        if (tid < G) {
+            // global-address-space pointer: a generic one may alias LDS, and every load then waits for the previous
+            // iteration's LDS store
+            const MST_GLOBAL_AS float* zg = (const MST_GLOBAL_AS float*)zx + (int64_t)bi * d.S * G + tid;
+            const int sstep = d.reverse ? -G : G;
+            zg += (int64_t)(d.reverse ? d.S - 1 - step : step) * G;
+            // sixteen (clamped, unconditional) loads in flight, then their LDS writes: a loop of runtime length left the
+            // compiler's remainder iterations (every step of an S = 4 launch) waiting out one round trip each
+            for (int i0 = 0; i0 < cnt; i0 += 16) {
+                float t[16];
+#pragma unroll
+                for (int i = 0; i < 16; ++i) t[i] = zg[(int64_t)min(i0 + i, cnt - 1) * sstep];
+#pragma unroll
+                for (int i = 0; i < 16; ++i) MST_PIN(t[i]);       // all landed here, the dropped ones too: none is waited for in a later step
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    if (i0 + i < cnt) zx_s[(i0 + i) * G + tid] = t[i];
+                }
+            }
+        }
+    };
+    if (REG) {
+        fetch(0);            // the first chunk is issued behind the weight and bias loads: one memory round trip for all three
+        // landed before the loop: the step loop then holds no load wait that would also drain its stores
 #pragma unroll
         for (int q = 0; q < 4; ++q) MST_PIN(bias[q]);
+        if (tid < G) {       // w[k] = W_hh[tid, k] or zero, sorted out only here: behind the wait the three kinds of load share
+#pragma unroll
+            for (int k4 = 0; k4 < 16; ++k4) {
+                const int sh = tid * H + 4 * k4 - min(tid * H + 4 * k4, wlast);       // 0 but at the end of the matrix
+                const lstm_f4u r = wv[k4];
+                float v0 = r.x, v1 = r.y, v2 = r.z;                   // selects, no branches; what a shift moves in from behind the
+                v0 = sh == 1 ? r.y : v0; v0 = sh == 2 ? r.z : v0; v0 = sh == 3 ? r.w : v0;      // matrix is dropped by k < H anyway
+                v1 = sh == 1 ? r.z : v1; v1 = sh == 2 ? r.w : v1;
+                v2 = sh == 1 ? r.w : v2;
+                w[4 * k4] = 4 * k4 < H ? v0 : 0.f; w[4 * k4 + 1] = 4 * k4 + 1 < H ? v1 : 0.f;
+                w[4 * k4 + 2] = 4 * k4 + 2 < H ? v2 : 0.f; w[4 * k4 + 3] = 4 * k4 + 3 < H ? r.w : 0.f;
+            }
+        }
     }
     if (tid < 256) h_s[tid] = 0.f;
     float c = 0.f;
@@ -66,18 +112,9 @@ __global__ __launch_bounds__(REG ? 256 : 1024) void lstm_fwd_kernel(const LstmDe
         const int64_t row = (int64_t)bi * d.S + s;
         float zn[4] = {0.f, 0.f, 0.f, 0.f};
         if (REG) {
-            if (step % zchunk == 0) {
-                if (step) MST_LDS_BARRIER();                 // the gate lanes are done with the previous chunk
-                const int cnt = min(zchunk, d.S - step);
-                if (tid < G) {
-                    // global-address-space pointer: a generic one may alias LDS, and every load then waits for the previous
-                    // iteration's LDS store
-                    const MST_GLOBAL_AS float* zg = (const MST_GLOBAL_AS float*)zx + (int64_t)bi * d.S * G + tid;
-                    const int sstep = d.reverse ? -G : G;
-                    zg += (int64_t)(d.reverse ? d.S - 1 - step : step) * G;
-#pragma unroll 8
-                    for (int i = 0; i < cnt; ++i) zx_s[i * G + tid] = zg[(int64_t)i * sstep];      // independent loads, all in flight
-                }
+            if (step % zchunk == 0 && step) {
+                MST_LDS_BARRIER();                           // the gate lanes are done with the previous chunk
+                fetch(step);
             }
         } else if (tid < H && step + 1 < d.S) {             // next step's zx row: in flight under this step's matvec
             const int sn = d.reverse ? s - 1 : s + 1;
@@ -320,7 +357,6 @@ __global__ __launch_bounds__(REG ? 256 : 1024) void lstm_bwd_kernel(const LstmDe
 // stores go through global-address-space pointers, so a barrier never drains them.  Summation orders are fixed (no atomics):
 // two runs are bit-identical.  H need not be a multiple of anything: the k (forward) / j (backward) ranges are padded to a
 // multiple of 16 with zero LDS operands and clamped weight rows.
-typedef float lstm_f4 __attribute__((ext_vector_type(4)));
 
 // Forward: lane l < H owns the four consecutive gate rows 4l .. 4l + 3 and reads them as ONE 16-byte load per k from W_hh^T
 // (rows of 4H floats: 16-byte aligned for any H).  k runs in four quarters that advance together (16 loads in flight per lane);
@@ -785,6 +821,60 @@ __global__ __launch_bounds__(256) void lstm_multi_fwd_kernel(const LstmDesc* __r
     }
 }
 
+// a * b + c as the device build of lstm_multi_bwd_kernel has always evaluated its three of them: ONE fma (hipcc contracts by
+// default).  Written out because which products get contracted otherwise depends on what the compiler vectorises around
+// them: with the operands coming from LDS it packed the multiplications in pairs first and the results moved by an ulp.  The
+// interpreter's x86-64 build does not contract and keeps its two roundings.
+#ifdef HIPSIM
+#define LSTM_MULADD(a, b, c) ((a) * (b) + (c))
+#else
+#define LSTM_MULADD(a, b, c) __builtin_fmaf((a), (b), (c))
+#endif
+
+// The G / 256 = 3 granules a lane of the backward kernel owns (256 apart), waited for JOINTLY: a poll round issues all the
+// loads, waits once and latches the values whose tag matches; only the rest are polled again, one s_sleep per round.  Three
+// gran_wait()s in a row cost three dependent memory round trips per step.  The failure contract is gran_wait's: the status
+// word is looked at every 256 rounds, the wait is bounded by LSTM_WAIT_TICKS, a timeout sets MST_DEV_LSTM_TIMEOUT, unmatched
+// values come back NaN and `dead` makes every later wait return at once.
+template <int N>
+__device__ __forceinline__ void gran_wait_joint(const lstm_gran_t* g, unsigned tag, int* status, bool& dead, float (&v)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = __builtin_nanf("");
+    if (dead) return;
+    long long t0 = 0;
+    unsigned need = (1u << N) - 1u;
+    for (unsigned spin = 0;; ++spin) {
+        lstm_gran_t x[N];
+#pragma unroll
+        for (int i = 0; i < N; ++i) {                    // every load of the round is issued before the first is looked at
+            x[i] = 0;
+            if ((need >> i) & 1u) x[i] = __hip_atomic_load(g + 256 * i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            if (((need >> i) & 1u) && (unsigned)(x[i] >> 32) == tag) { v[i] = __uint_as_float((unsigned)x[i]); need &= ~(1u << i); }
+        }
+        if (!need) return;
+        __builtin_amdgcn_s_sleep(1);
+        if ((spin & 255u) == 255u) {                     // off the fast path: a healthy wait ends within a few polls
+            if (__hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;      // somebody gave up
+            const long long now = wall_clock64();
+            if (spin == 255u) t0 = now;
+            else if (now - t0 > LSTM_WAIT_TICKS) { __hip_atomic_fetch_or(status, MST_DEV_LSTM_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
+        }
+    }
+    dead = true;
+}
+
+// Backward.  What sits on the exchange chain of a step is: gate math out of LDS-staged operands -> four granule stores -> ONE
+// joint poll of the lane's three granules -> matvec.  (1) The streamed operands (four saved gates, tc, c_prev, the incoming
+// gradient) of LSTM_MCH steps are staged at once by wave 0 into LDS slots only wave 0 touches (wave-private: MST_WAVE_SYNC, no
+// barrier) — fetched one step ahead they were waited out (vmcnt(0)) in front of the gate math of every step.  (2) The three
+// sequential gran_wait()s are one gran_wait_joint().  (3) The four gz stores are issued AFTER the poll of their step, so the
+// poll's wait covers only the granule stores and its own loads, and they have about a step to retire before the next poll.
+// (4) The W_hh registers are pinned before the loop: the matvec's waits for them (vmcnt is in-order: they ended in a
+// vmcnt(0) that drained the step's stores) are gone.  In the gfx950 assembly a step body now holds no s_waitcnt vmcnt but
+// the poll's own (and, every LSTM_MCH steps, the refill's).
 __global__ __launch_bounds__(256) void lstm_multi_bwd_kernel(const LstmDesc* __restrict__ descs, Bases b) {
     const LstmDesc d = descs[blockIdx.y];
     constexpr int H = LSTM_MH, G = 4 * H, HU = H / LSTM_NB, JQ = 16, JW = G / JQ;   // 16 j-chunks of 48 gate rows
@@ -792,9 +882,11 @@ __global__ __launch_bounds__(256) void lstm_multi_bwd_kernel(const LstmDesc* __r
     const int kk = tid & (HU - 1), jq = tid / HU;             // lane (jq, kk) sums W_hh[jq*48 + i][wg*16 + kk] dz[jq*48 + i]
     MST_COOP_LDS(dz_s, G);
     MST_COOP_LDS2(part_s, JQ, HU + 1);
+    MST_COOP_LDS(sv_s, LSTM_MCH * 7 * HU);
     const float* whh = b.p[SP_PAR] + d.whh_off;
-    const float* tmp = b.p[SP_TMP];
+    const MST_GLOBAL_AS float* tmp = (const MST_GLOBAL_AS float*)b.p[SP_TMP];      // not generic: cannot alias the LDS staging
     float* gr = b.p[SP_GRAD];
+    const MST_GLOBAL_AS float* grg = (const MST_GLOBAL_AS float*)gr;
     int* status = reinterpret_cast<int*>(b.p[SP_WS] + d.status_off);
     bool dead = false;
     lstm_gran_t* xch = reinterpret_cast<lstm_gran_t*>(b.p[SP_TMP] + d.xch_off) + 2 * H;     // [2][G], behind the forward's
@@ -803,46 +895,68 @@ __global__ __launch_bounds__(256) void lstm_multi_bwd_kernel(const LstmDesc* __r
     for (int i = 0; i < JW; ++i) w[i] = whh[(int64_t)(jq * JW + i) * H + wg * HU + kk];
     const int k = wg * HU + (tid < HU ? tid : 0);
     float dc_next = 0.f, dh_rec = 0.f;
-    float sv[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#define LSTM_MLOAD(STEP, DST)                                                                           \
+#define LSTM_MLOAD(STEP, K, DST)                                                                        \
     {                                                                                                   \
         const int s_ = d.reverse ? d.S - 1 - (STEP) : (STEP);                                           \
         const int sp_ = d.reverse ? s_ + 1 : s_ - 1;                                                    \
-        const float* g_ = tmp + d.gates_off + (int64_t)s_ * G;                                          \
-        DST[0] = g_[k]; DST[1] = g_[H + k]; DST[2] = g_[2 * H + k]; DST[3] = g_[3 * H + k];             \
-        DST[4] = tmp[d.tc_off + (int64_t)s_ * H + k];                                                   \
-        DST[5] = (STEP) > 0 ? tmp[d.c_off + (int64_t)sp_ * H + k] : 0.f;                                \
-        DST[6] = gr[d.gout_off + (int64_t)s_ * d.out_ld + k];                                           \
+        const MST_GLOBAL_AS float* g_ = tmp + d.gates_off + (int64_t)s_ * G;                            \
+        DST[0] = g_[K]; DST[1] = g_[H + K]; DST[2] = g_[2 * H + K]; DST[3] = g_[3 * H + K];             \
+        DST[4] = tmp[d.tc_off + (int64_t)s_ * H + K];                                                   \
+        const float cp_ = tmp[d.c_off + (int64_t)((STEP) > 0 ? sp_ : s_) * H + K];      /* unconditional (clamped): no branch */ \
+        DST[5] = (STEP) > 0 ? cp_ : 0.f;                                                                \
+        DST[6] = grg[d.gout_off + (int64_t)s_ * d.out_ld + K];                                          \
     }
-    if (tid < HU) LSTM_MLOAD(d.S - 1, sv)
+    // wave 0: the operands of the LSTM_MCH steps from `step` down; lane (tid / HU, tid % HU) takes every fourth step of unit tid % HU
+    auto stage = [&](const int step) {
+        const int cnt = min(LSTM_MCH, step + 1), ku = wg * HU + kk;
+#pragma unroll 4
+        for (int i = jq; i < cnt; i += 64 / HU) {             // independent loads, 28 in flight
+            float t[7];
+            LSTM_MLOAD(step - i, ku, t)
+#pragma unroll
+            for (int q = 0; q < 7; ++q) sv_s[(i * 7 + q) * HU + kk] = t[q];
+        }
+        MST_WAVE_SYNC();
+    };
+    if (tid < 64) stage(d.S - 1);        // behind the W_hh loads: one wait for all of them
+#pragma unroll
+    for (int i = 0; i < JW; ++i) MST_PIN(w[i]);               // landed here: the matvec of a step waits on nothing
     for (int step = d.S - 1; step >= 0; --step) {
         const int s = d.reverse ? d.S - 1 - step : step;
         const unsigned epoch = (unsigned)(d.S - step);        // 1, 2, ... in execution order
         const int par = (int)(epoch & 1);
-        float nx[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        const int slot = (d.S - 1 - step) % LSTM_MCH;
+        if (tid < 64 && slot == 0 && step != d.S - 1) stage(step);
+        float dzi = 0.f, dzf = 0.f, dzg = 0.f, dzo = 0.f;
         if (tid < HU) {
-            if (step > 0) LSTM_MLOAD(step - 1, nx)
+            float sv[7];
+#pragma unroll
+            for (int q = 0; q < 7; ++q) sv[q] = sv_s[(slot * 7 + q) * HU + tid];
             const float ig = sv[0], fg = sv[1], gg = sv[2], og = sv[3], tc = sv[4], cprev = sv[5];
             const float dh = sv[6] + dh_rec;
-            const float dc = dc_next + dh * og * (1.f - tc * tc);
-            const float dzi = dc * gg * ig * (1.f - ig);
-            const float dzf = dc * cprev * fg * (1.f - fg);
-            const float dzg = dc * ig * (1.f - gg * gg);
-            const float dzo = dh * tc * og * (1.f - og);
+            const float dc = LSTM_MULADD(dh * og, LSTM_MULADD(-tc, tc, 1.f), dc_next);      // dc_next + dh * og * (1 - tc * tc)
+            dzi = dc * gg * ig * (1.f - ig);
+            dzf = dc * cprev * fg * (1.f - fg);
+            dzg = dc * ig * LSTM_MULADD(-gg, gg, 1.f);                                          // dc * ig * (1 - gg * gg)
+            dzo = dh * tc * og * (1.f - og);
             dc_next = dc * fg;
             if (step > 0) {                                   // the last step's dz feeds no further recurrence
                 lstm_gran_t* x = xch + par * G;
                 gran_store(x + k, epoch, dzi); gran_store(x + H + k, epoch, dzf);
                 gran_store(x + 2 * H + k, epoch, dzg); gran_store(x + 3 * H + k, epoch, dzo);
             }
+        }
+        if (step > 0) {
+            float dzv[G / 256];
+            gran_wait_joint(xch + par * G + tid, epoch, status, dead, dzv);
+#pragma unroll
+            for (int i = 0; i < G / 256; ++i) dz_s[tid + 256 * i] = dzv[i];
+        }
+        if (tid < HU) {                                       // behind the poll: off the path between publish and poll
             float* gz = gr + d.gzx_off + (int64_t)s * G;
             gz[k] = dzi; gz[H + k] = dzf; gz[2 * H + k] = dzg; gz[3 * H + k] = dzo;
-#pragma unroll
-            for (int q = 0; q < 7; ++q) sv[q] = nx[q];
         }
         if (step == 0) break;
-#pragma unroll
-        for (int i = 0; i < G / 256; ++i) dz_s[tid + 256 * i] = gran_wait(xch + par * G + tid + 256 * i, epoch, status, dead);
         __syncthreads();
         float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
 #pragma unroll
