@@ -263,6 +263,24 @@ int32_t mst_hard_output(float* x, float* out, int64_t n_pos, int32_t nfeat, mst_
 int32_t mst_clip_scatter(const int32_t* cells, const float* feats, const int32_t* counts, int32_t capacity, int32_t n_clips,
                          int64_t n_cells, int32_t nfeat, float* out, mst_stream stream);
 
+/* ---- windowed clips: K same-shaped clips cut out of differently long songs whose records stay on the device.
+ * cells / feats are a POOL holding the records of many songs back to back; win[k] (a DEVICE array, read ON THE DEVICE: a
+ * captured graph replays with other songs and other windows) describes clip k:
+ *   first, count   the song's records are cells[first, first + count) (and the matching feats rows): the strictly ascending
+ *                  flat cell indices of a roll (channels, src_bars, bar_cells); count is clamped at 0, a negative first
+ *                  reads as no records
+ *   src_bars       bars of that song;  r0  the first bar of the window, may be negative or reach past the end
+ * out: n_clips x channels x bars x bar_cells x nfeat floats; out[k, c, r, j, :] is the source cell (c, r0 + r, j) when
+ * 0 <= r0 + r < src_bars, else +0.0 — i.e. x[:, r0:r0 + bars] of the dense song, zero-extended.  bar_cells is T*10*56 for a
+ * pitched roll and T*10*47 (channels = 1) for an unpitched one.  mst_clip_scatter's promises hold: EVERY float of out is
+ * written exactly once (no clearing, stale or NaN contents disappear), nothing outside out is written, out needs float
+ * alignment only, no atomics (bit-reproducible), one launch, enqueue-only on `stream`, capturable; a record whose cell lies
+ * outside its song's roll is skipped, never stored (a song of 2^31 cells or more reads as silence).  MST_ERR_ARG: null
+ * pointer, nfeat outside {2, 5}, n_clips / channels / bars / bar_cells < 1, channels * bars * bar_cells >= 2^31. */
+typedef struct { int32_t first, count, src_bars, r0; } mst_window;   /* 16 bytes */
+int32_t mst_clip_window(const int32_t* cells, const float* feats, const mst_window* win, int32_t n_clips, int32_t channels,
+                        int32_t bars, int64_t bar_cells, int32_t nfeat, float* out, mst_stream stream);
+
 /* ---- sparse clip output: the sorted note records of a dense roll, built on the device — the inverse of mst_clip_scatter, so
  * that inference downloads the notes (24 bytes per pitched record) instead of the whole roll.  x: n_cells x nfeat floats.
  *   MST_ROLL_NONZERO  a cell is a record when the float32 BIT PATTERN of any of its features is non-zero (-0.0 and NaN are

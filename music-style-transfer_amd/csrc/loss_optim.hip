@@ -874,6 +874,91 @@ extern "C" int32_t mst_clip_scatter(const int32_t* cells, const float* feats, co
     return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
 }
 
+// ------------------------------------------------------------------ windowed clips (mst_clip_window)
+// K clips of one shape cropped out of songs of any length whose records sit in a device pool.  The destination is cut into the
+// same slices as above.  A (clip, channel) SLAB of it — bars x bar_cells cells — is the source cells [t0, t1) of that song's
+// channel shifted by a constant, so a slice runs one search pair per slab it overlaps (several at the smallest shapes: an
+// unpitched slab of one bar at T = 1 is 940 floats) and drops the records found into its LDS image exactly as the scatter does.
+// The descriptors are read here, on the device: a captured launch replays with other songs and windows.
+template <int NFEAT>
+__global__ __launch_bounds__(SCAT_THREADS) void clip_window_kernel(const int32_t* cells, const float* feats, const mst_window* win,
+                                                                   int channels, int bars, int64_t bar_cells, int64_t total,
+                                                                   float* out, int shift) {
+    __shared__ float4 img4[SCAT_SLICE / 4];
+    __shared__ int flag[2 * SCAT_THREADS], sel[2];
+    float* img = reinterpret_cast<float*>(img4);
+    const int tid = threadIdx.x;
+    const int64_t gb = (int64_t)blockIdx.x * SCAT_SLICE;
+    const int64_t g0 = gb > shift ? gb : shift;
+    const int64_t g1 = gb + SCAT_SLICE < shift + total ? gb + SCAT_SLICE : shift + total;
+    for (int i = tid; i < SCAT_SLICE / 4; i += SCAT_THREADS) img4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    __syncthreads();
+    const int64_t slab_cells = (int64_t)bars * bar_cells, per = slab_cells * NFEAT, f0 = g0 - shift, f1 = g1 - shift;
+    for (int64_t s = f0 / per; s * per < f1; ++s) {                  // the slabs this slice touches; everything here is uniform
+        const int64_t lo = f0 > s * per ? f0 - s * per : 0;          // slab-local floats [lo, hi) of this slice
+        const int64_t hi = f1 - s * per < per ? f1 - s * per : per;
+        const mst_window w = win[s / channels];
+        const int64_t c = s % channels;
+        const int64_t roll_bars = (int64_t)channels * w.src_bars;    // a song of 2^31 cells or more has no int32 cell indices
+        if (w.count <= 0 || w.first < 0 || w.src_bars < 1 || roll_bars >= ((int64_t)1 << 31) ||
+            roll_bars * bar_cells >= ((int64_t)1 << 31))
+            continue;
+        // slab-local cells [d0, d1): those of the slice whose bar r0 + d / bar_cells exists in the song
+        const int64_t v0 = w.r0 < 0 ? -(int64_t)w.r0 * bar_cells : 0;
+        const int64_t left = (int64_t)w.src_bars - w.r0;             // bars of the song from r0 on (<= 0: wholly past the end)
+        const int64_t v1 = left <= 0 ? 0 : (left < bars ? left * bar_cells : slab_cells);
+        int64_t d0 = lo / NFEAT, d1 = (hi + NFEAT - 1) / NFEAT;
+        d0 = d0 > v0 ? d0 : v0;
+        d1 = d1 < v1 ? d1 : v1;
+        if (d0 >= d1) continue;
+        const int64_t off = (c * w.src_bars + w.r0) * bar_cells;     // source cell = slab-local cell + off, in [0, roll_cells)
+        const int t0 = (int)(d0 + off), t1 = (int)(d1 + off);
+        const int32_t* ck = cells + w.first;
+        const float* fk = feats + (int64_t)w.first * NFEAT;
+        int r0, r1;
+        scatter_bounds(ck, w.count, t0, t1, flag, sel, r0, r1);
+        for (int64_t e = tid; e < (int64_t)(r1 - r0) * NFEAT; e += SCAT_THREADS) {
+            const int64_t r = r0 + e / NFEAT;
+            const int64_t cell = ck[r];
+            const int64_t local = (cell - off) * NFEAT + e % NFEAT;
+            // on cells that are not ascending the search may hand over anything: only a cell of [t0, t1) is a cell of this slab
+            if (cell >= t0 && cell < t1 && local >= lo && local < hi) img[s * per + local + shift - gb] = fk[r * NFEAT + e % NFEAT];
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < SCAT_SLICE / 4; i += SCAT_THREADS) {
+        const int64_t g = gb + 4 * i;
+        if (g >= g0 && g + 4 <= g1) {
+            *reinterpret_cast<float4*>(out + (g - shift)) = img4[i];
+        } else {                                                      // the ragged head and tail of the destination
+            for (int j = 0; j < 4; ++j)
+                if (g + j >= g0 && g + j < g1) out[g + j - shift] = img[4 * i + j];
+        }
+    }
+}
+
+extern "C" int32_t mst_clip_window(const int32_t* cells, const float* feats, const mst_window* win, int32_t n_clips, int32_t channels,
+                                   int32_t bars, int64_t bar_cells, int32_t nfeat, float* out, mst_stream stream) {
+    if (!cells || !feats || !win || !out || n_clips < 1 || channels < 1 || bars < 1 || bar_cells < 1 || (nfeat != 5 && nfeat != 2) ||
+        ((uintptr_t)out & 3))
+        return MST_ERR_ARG;
+    if (bar_cells >= ((int64_t)1 << 31) || (int64_t)channels * bars >= ((int64_t)1 << 31) ||
+        (int64_t)channels * bars * bar_cells >= ((int64_t)1 << 31))
+        return MST_ERR_ARG;
+    const int shift = (int)(((uintptr_t)out & 15) / 4);
+    const int64_t total = (int64_t)n_clips * channels * bars * bar_cells * nfeat;
+    const int64_t nb = (shift + total + SCAT_SLICE - 1) / SCAT_SLICE;
+    if (nb > 0x7fffffff) return MST_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    if (nfeat == 5)
+        hipLaunchKernelGGL(clip_window_kernel<5>, dim3((unsigned)nb), dim3(SCAT_THREADS), 0, s, cells, feats, win, (int)channels,
+                           (int)bars, bar_cells, total, out, shift);
+    else
+        hipLaunchKernelGGL(clip_window_kernel<2>, dim3((unsigned)nb), dim3(SCAT_THREADS), 0, s, cells, feats, win, (int)channels,
+                           (int)bars, bar_cells, total, out, shift);
+    return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
+}
+
 // ------------------------------------------------------------------ sparse clip output (mst_roll_count, mst_roll_compact)
 // The inverse of the scatter: the sorted (cell, features) records of a dense roll, so that only the notes go back to the host.
 // An ordered stream compaction in the usual three steps — per-slice counts, an exclusive scan of the counts, emit — with no atomics

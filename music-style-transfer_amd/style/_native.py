@@ -45,6 +45,7 @@ class PlanOptions(C.Structure):
 
 DEV_LSTM_TIMEOUT = 1        # mst_amd.h MST_DEV_LSTM_TIMEOUT
 ROLL_NONZERO, ROLL_HARD = 0, 1      # mst_amd.h MST_ROLL_*: record modes of mst_roll_count / mst_roll_compact
+WINDOW_WORDS = 4                    # mst_amd.h mst_window: int32 words per descriptor of mst_clip_window (first, count, src_bars, r0)
 METRIC_WORDS = 8                    # mst_amd.h MST_METRIC_WORDS: doubles per record of mst_roll_metrics / mst_eval_iteration
 
 
@@ -113,6 +114,7 @@ _SIGS = {
                                           C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, _P]),
     'mst_hard_output': (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P]),
     'mst_clip_scatter': (C.c_int32, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _P, _P]),
+    'mst_clip_window': (C.c_int32, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _P, _P]),
     'mst_roll_slices': (C.c_int64, [C.c_int64]),
     'mst_roll_count': (C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
     'mst_roll_compact': (C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P]),
@@ -192,6 +194,14 @@ class Native:
         addr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()
         check(self.lib.mst_clip_scatter(addr(cells), addr(feats), addr(counts), int(capacity), int(n_clips), int(n_cells), int(nfeat),
                                         addr(out), stream), 'mst_clip_scatter')
+
+    def clip_window(self, cells, feats, win, out, n_clips, channels, bars, bar_cells, nfeat, stream=None):
+        """mst_clip_window: `out` (n_clips x channels x bars x bar_cells x nfeat floats) cropped out of the songs of a record
+        pool.  `cells` (int32) / `feats` (float32) are the pool, `win` the n_clips descriptors (int32 rows of WINDOW_WORDS:
+        first, count, src_bars, r0), read on the device.  Tensors on out's device or raw addresses.  Enqueue-only."""
+        addr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()
+        check(self.lib.mst_clip_window(addr(cells), addr(feats), addr(win), int(n_clips), int(channels), int(bars), int(bar_cells),
+                                       int(nfeat), addr(out), stream), 'mst_clip_window')
 
     def roll_slices(self, n_cells):
         """mst_roll_slices: slices the compaction kernels cut `n_cells` into; the workspace of roll_count holds one int32 more."""

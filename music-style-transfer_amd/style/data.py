@@ -3,7 +3,8 @@ one-hot encoding, MIDI file -> model input (`iter_inputs`, `get_input`), `prepar
 `get_used_instruments`.  Everything here runs on the host, per song; only `prepare_input` touches the
 device (one H2D copy per tensor).  `prepare_input_sparse` is its counterpart for real songs: the note
 tensors stay on the host as sorted note records (`SparseRoll`, `SparseClip`) and are expanded on the
-device by mst_clip_scatter.  sklearn's OneHotEncoder and pandas are not used: categories are the
+device by mst_clip_scatter.  `SongStore` keeps the records of many songs on the device and `WindowBatch` names K equally
+shaped windows of them (mst_clip_window crops them there).  sklearn's OneHotEncoder and pandas are not used: categories are the
 sorted distinct values, which is what `categories='auto'` produces (style/data.py:23-27).
 """
 import numpy as np
@@ -197,6 +198,193 @@ class SparseClip:
             roll = lambda key: SparseRoll(z[f'{key}_cells'], z[f'{key}_feats'], z[f'{key}_shape']) if f'{key}_cells' in z else None
             target = z['bpm_target'].item()
             return cls(z['mode'], z['bpm'], roll('pitched'), z['instruments_features'], roll('unpitched'), target)
+
+
+class WindowBatch:
+    """K windows of `bars` bars of one shape, as `SongStore.sample` draws them: clip k is bars [r0s[k], r0s[k] + bars) of song
+    `songs[k]` of the store.  `C`, `T`, `percussion` are the bucket's; all K clips share them, so one batched plan runs them."""
+
+    def __init__(self, C, bars, T, percussion, songs, r0s):
+        self.C, self.bars, self.T, self.percussion = int(C), int(bars), int(T), bool(percussion)
+        self.songs, self.r0s = np.asarray(songs, dtype=np.int64), np.asarray(r0s, dtype=np.int64)
+        if self.songs.ndim != 1 or self.songs.shape != self.r0s.shape or not len(self.songs):
+            raise ValueError('songs and r0s: two equally long 1-d lists, one entry per clip')
+
+    @property
+    def K(self):
+        return len(self.songs)
+
+    def __repr__(self):
+        return (f'WindowBatch(C={self.C}, bars={self.bars}, T={self.T}, percussion={self.percussion}, '
+                f'songs={self.songs.tolist()}, r0s={self.r0s.tolist()})')
+
+
+class _RecordPool:
+    """The records of many songs back to back on the device: `cells` int32 (capacity,), `feats` float32 (capacity, nfeat)."""
+
+    def __init__(self, nfeat, device, capacity):
+        self.nfeat, self.used = nfeat, 0
+        self.cells = torch.zeros(capacity, dtype=torch.int32, device=device)
+        self.feats = torch.zeros(capacity, nfeat, dtype=torch.float32, device=device)
+
+    def append(self, roll):
+        """-> `first`: the roll's records are [first, first + roll.count) of the pool."""
+        need = self.used + roll.count
+        if need > self.cells.numel():
+            _not_while_capturing(self.cells.device)
+            capacity = self.cells.numel()
+            while capacity < need:
+                capacity *= 2
+            cells, feats = self.cells.new_zeros(capacity), self.feats.new_zeros(capacity, self.nfeat)
+            cells[:self.used].copy_(self.cells[:self.used])
+            feats[:self.used].copy_(self.feats[:self.used])
+            self.cells, self.feats = cells, feats         # (the old ones are recycled in stream order)
+        first = self.used
+        self.cells[first:need].copy_(roll.cells, non_blocking=True)
+        self.feats[first:need].copy_(roll.feats, non_blocking=True)
+        self.used = need
+        return first
+
+
+def _not_while_capturing(dev):
+    if dev.type == 'cuda' and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError('SongStore: a device pool or table would have to grow while a stream is capturing; add the songs first')
+
+
+class SongStore:
+    """Songs resident on the device, for training on windows of them (StyleTransferModel.train_windows).  `add` appends a
+    song's pitched and unpitched note records to two device pools (grown by doubling, never during a capture) and its small
+    inputs — mode, bpm, instrument features, used instruments, bpm target — as a row of a device table; the host keeps the
+    cells, `(C, R, T)` and the percussion flag.  Songs are bucketed by `(C, T, has percussion)`: the windows of one bucket have
+    one shape once their number of bars is chosen, which is what a batched plan needs.  `sample` draws K windows of a bucket;
+    mst_clip_window crops them on the device, so no note data crosses the bus inside the training loop."""
+    TRIES = 8             # windows tried per drawn song before another song is drawn
+
+    def __init__(self, device=device, capacity=1 << 14):
+        self.device = torch.device(device)
+        self.songs = []                                   # per song id: dict of host-side facts
+        self.pools = {n_feat: _RecordPool(n_feat, self.device, capacity) for n_feat in (5, 2)}
+        self.buckets = {}                                 # (C, T, percussion) -> dict(songs, table, fields)
+        self._silent = set()                              # (song, bars): no window of that many bars passes the silence rule
+
+    def __len__(self):
+        return len(self.songs)
+
+    def add(self, clip):
+        """Take a SparseClip in; returns the song's id.  A clip whose percussion is silent is stored without it, as
+        `SparseClip.drop_silent` would; one without pitched notes is refused (ValueError)."""
+        clip = clip.drop_silent()
+        if clip is None:
+            raise ValueError('SongStore.add: the clip has no pitched notes (SparseClip.drop_silent() is None)')
+        pitched, unpitched = clip.pitched_channels, clip.unpitched_channels
+        _, C, R, T = pitched.shape[:4]
+        if unpitched is not None and tuple(unpitched.shape[:4]) != (1, 1, R, T):
+            raise ValueError(f'unpitched roll {unpitched.shape} does not match the pitched roll {pitched.shape}')
+        key = (C, T, unpitched is not None)
+        used = get_used_instruments(clip.instruments_features, unpitched)
+        row = torch.cat([t.reshape(-1).float() for t in (clip.mode, clip.bpm, clip.instruments_features, used,
+                                                         torch.tensor([float(clip.bpm_target)]))])
+        bucket = self.buckets.get(key)
+        if bucket is None:
+            sizes = [clip.mode.numel(), clip.bpm.numel(), clip.instruments_features.numel(), used.numel(), 1]
+            ends = np.cumsum(sizes).tolist()
+            bucket = self.buckets[key] = dict(songs=[], fields=list(zip([0] + ends[:-1], ends)), views={},
+                                              table=torch.zeros(16, ends[-1], dtype=torch.float32, device=self.device))
+        if row.numel() != bucket['table'].shape[1]:
+            raise ValueError(f'small inputs of {row.numel()} floats, the bucket {key} holds rows of {bucket["table"].shape[1]}')
+        at = len(bucket['songs'])
+        if at == bucket['table'].shape[0]:
+            _not_while_capturing(self.device)
+            table = bucket['table'].new_zeros(2 * at, row.numel())
+            table[:at].copy_(bucket['table'])
+            bucket['table'], bucket['views'] = table, {}
+        bucket['table'][at].copy_(row)
+        sounding = lambda roll: roll.cells.numpy()[np.any(roll.feats.numpy() != 0, axis=1)].astype(np.int64)
+        song = dict(C=C, R=R, T=T, percussion=unpitched is not None, key=key, row=at,
+                    pitched=(self.pools[5].append(pitched), pitched.count), pitched_cells=sounding(pitched), unpitched=None)
+        if unpitched is not None:
+            song.update(unpitched=(self.pools[2].append(unpitched), unpitched.count), unpitched_cells=sounding(unpitched))
+        self.songs.append(song)
+        bucket['songs'].append(len(self.songs) - 1)
+        return len(self.songs) - 1
+
+    def bucket_of(self, song):
+        return self.songs[song]['key']
+
+    # ---- windows
+    def window_sounds(self, song, r0, bars):
+        """train-model.py:105-109 applied to a window: it holds a sounding pitched note and, for a song with percussion, a
+        sounding unpitched one (a silent roll makes the loss's masked means 0 / 0).  Decided on the host cells."""
+        s = self.songs[song]
+        per_bar = s['T'] * 10 * 56
+        bounds = [(c * s['R'] + r0 + b) * per_bar for c in range(s['C']) for b in (0, bars)]
+        at = np.searchsorted(s['pitched_cells'], bounds).reshape(-1, 2)
+        if not np.any(at[:, 1] > at[:, 0]):
+            return False
+        if s['percussion']:
+            per_bar = s['T'] * 10 * 47
+            lo, hi = np.searchsorted(s['unpitched_cells'], [r0 * per_bar, (r0 + bars) * per_bar])
+            return bool(hi > lo)
+        return True
+
+    def sample(self, rng, K, bars):
+        """K windows of `bars` bars from ONE bucket -> WindowBatch, or None when no bucket can fill K slots.  The bucket is
+        picked with probability proportional to its eligible songs (R >= bars); each slot draws a song uniformly from them and
+        a first bar uniformly from [0, R - bars], keeps the window if `window_sounds`, tries up to 8 first bars and then
+        draws another song.  `rng`: a numpy.random.Generator; the same generator state gives the same batch."""
+        K, bars = int(K), int(bars)
+        if K < 1 or bars < 1:
+            raise ValueError('sample: K and bars must be at least 1')
+        eligible = {key: [s for s in b['songs'] if self.songs[s]['R'] >= bars and (s, bars) not in self._silent]
+                    for key, b in self.buckets.items()}
+        while True:
+            keys = [key for key in sorted(eligible) if eligible[key]]
+            if not keys:
+                return None
+            weights = np.array([len(eligible[key]) for key in keys], dtype=np.float64)
+            key = keys[int(rng.choice(len(keys), p=weights / weights.sum()))]
+            songs, r0s = [], []
+            pick = eligible[key]
+            while pick and len(songs) < K:
+                song = pick[int(rng.integers(len(pick)))]
+                last = self.songs[song]['R'] - bars
+                for _ in range(self.TRIES):
+                    r0 = int(rng.integers(0, last + 1))
+                    if self.window_sounds(song, r0, bars):
+                        songs.append(song)
+                        r0s.append(r0)
+                        break
+                else:
+                    # eight misses: is there a window at all?  A song without one is not drawn again for this length
+                    if not any(self.window_sounds(song, r0, bars) for r0 in range(last + 1)):
+                        self._silent.add((song, bars))
+                        pick.remove(song)
+            if len(songs) == K:
+                return WindowBatch(key[0], bars, key[1], key[2], songs, r0s)
+
+    def describe(self, batch, out):
+        """Fill `out` (a host int32 array (2, K, 4)) with the mst_window descriptors of the batch: row 0 for the pitched
+        rolls, row 1 for the unpitched ones (zeros without percussion)."""
+        out[:] = 0
+        for k, (song, r0) in enumerate(zip(batch.songs.tolist(), batch.r0s.tolist())):
+            s = self.songs[song]
+            if s['key'] != (batch.C, batch.T, batch.percussion):
+                raise ValueError(f'song {song} is of bucket {s["key"]}, the batch of {(batch.C, batch.T, batch.percussion)}')
+            out[0, k] = (*s['pitched'], s['R'], r0)
+            if s['percussion']:
+                out[1, k] = (*s['unpitched'], s['R'], r0)
+
+    def small_inputs(self, batch):
+        """Views of the table rows of the batch's songs, clip by clip: mode, bpm, instrument features, used instruments, bpm
+        target (the order of the plan's input slots)."""
+        bucket = self.buckets[(batch.C, batch.T, batch.percussion)]
+        views, out = bucket['views'], []
+        for song in batch.songs.tolist():
+            if song not in views:
+                row = bucket['table'][self.songs[song]['row']]
+                views[song] = [row[a:b] for a, b in bucket['fields']]
+            out += views[song]
+        return out
 
 
 def prepare_input_sparse(input, max_n_bars=None, pin=None):

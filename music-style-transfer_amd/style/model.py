@@ -49,11 +49,12 @@ def get_mean_size(*values, factor=1):
     return math.ceil(np.mean(values) * factor)
 
 
-def _dims(C=1, R=1, T=1, unpitched=True, **widths):
+def _dims(C=1, R=1, T=1, unpitched=True, clips=0, **widths):
     w = dict(_DEFAULT_WIDTHS)
     w.update(widths)
     return _native.Dims(C=C, R=R, T=T, beat=w['beat'], bar=w['bar'], nrf=w['nrf'], style=w['style'], melody=w['melody'],
-                        rhythm=w['rhythm'], instr=w['instr'], n_instruments=w['n_instruments'], has_unpitched=int(unpitched))
+                        rhythm=w['rhythm'], instr=w['instr'], n_instruments=w['n_instruments'], has_unpitched=int(unpitched),
+                        clips=clips)
 
 
 class _Container(nn.Module):
@@ -342,8 +343,8 @@ class StyleTransferModel(nn.Module):
             if p.grad is None:
                 p.grad = self._gflat[off:off + p.numel()].view(p.shape)
 
-    def _plan(self, C, R, T, unpitched, dev):
-        return _native.get().plan(_dims(C=C, R=R, T=T, unpitched=unpitched, **self._widths), dev)
+    def _plan(self, C, R, T, unpitched, dev, clips=0):
+        return _native.get().plan(_dims(C=C, R=R, T=T, unpitched=unpitched, clips=clips, **self._widths), dev)
 
     def _anchor(self):
         self._sync_flat()
@@ -487,6 +488,85 @@ class StyleTransferModel(nn.Module):
         metrics = torch.empty(C + 2, _native.METRIC_WORDS, dtype=torch.float64, device=dev)
         plan.eval_iteration(self._flat, st['pitched'], st['unpitched'], losses, metrics, ws=ws)
         return EvalResult(losses, metrics)
+
+    def train_windows(self, store, batch):
+        """K loop bodies in ONE batched pass: the K windows of `batch` (style.data.WindowBatch, drawn by `store.sample`) of the
+        songs resident in `store` (style.data.SongStore, on the model's device) go through the `clips = K` plan of their shape.
+        No note data is uploaded: the K window descriptors (16 bytes per clip and roll) travel as one copy from pinned memory,
+        two mst_clip_window launches crop the windows out of the store's record pools into the plan's static note buffers,
+        one _foreach_copy_ moves the clips' small inputs from the store's table into their workspace slots, and
+        mst_train_iteration runs forward, loss and backward of all K clips.  The gradient of the K clips is ADDED to the
+        model's gradient buffer (the sum over the clips, as K train_iteration calls would leave it), ready for
+        optimizer.step().  Returns the K x 15 loss leaves (key order style._native.LOSS_KEYS) on the device; nothing is read
+        back.  From the second use of a plan on, the two crops and the pass replay as one hipGraph: the descriptors are read
+        on the device, so a replay serves other songs and other windows.
+
+        It runs on the current stream, behind whatever train_iteration has enqueued on its lanes (their bookkeeping is left
+        alone), in a workspace and note buffers of its own per plan: it touches neither lane 1's gradient buffer nor the lane
+        counter."""
+        anchor = self._anchor()
+        dev = anchor.device
+        if store.pools[n_pitched_features].cells.device != dev:
+            raise _native.MstError(f'the SongStore lives on {store.device}, the model on {dev}')
+        K, C, R, T, U = batch.K, batch.C, batch.bars, batch.T, batch.percussion
+        plan = self._plan(C, R, T, U, dev, clips=K)
+        st = plan.__dict__.get('_window_state')
+        if st is None:
+            ws = plan.new_ws()
+            roll = lambda *shape: torch.empty((K,) + shape, dtype=torch.float32, device=dev)
+            st = plan.__dict__['_window_state'] = dict(
+                ws=ws, pitched=roll(C, R, T, n_beat_fractions, n_pitched_notes, n_pitched_features),
+                unpitched=roll(1, R, T, n_beat_fractions, n_unpitched_notes, n_unpitched_features) if U else None,
+                losses=torch.empty(K, _native.N_LOSSES, dtype=torch.float32, device=dev),
+                win=torch.zeros(2, K, _native.WINDOW_WORDS, dtype=torch.int32, device=dev),
+                # pinned staging slots of the descriptors, each reused only after the copy that last read it (its event)
+                stage=[dict(buf=torch.zeros(2, K, _native.WINDOW_WORDS, dtype=torch.int32, pin_memory=dev.type == 'cuda'), done=None)
+                       for _ in range(4)],
+                slots=[plan.view(n, ws=ws, clip=k) for k in range(K)
+                       for n in ('mode', 'bpm', 'instr', 'used_instruments', 'bpm_target')],
+                at=0, graph=None, key=None, uses=0)
+        ws = st['ws']
+        self.join_lanes_keep()
+        gflat = self._grad_target()
+        stage = st['stage'][st['at'] % len(st['stage'])]
+        st['at'] += 1
+        if stage['done'] is not None and not stage['done'].query():
+            stage['done'].synchronize()
+        store.describe(batch, stage['buf'].numpy())
+        st['win'].copy_(stage['buf'], non_blocking=True)
+        if dev.type == 'cuda':
+            stage['done'] = stage['done'] or torch.cuda.Event()
+            stage['done'].record()
+        torch._foreach_copy_(st['slots'], store.small_inputs(batch))
+        pools = store.pools
+        stream = _native.current_stream
+
+        def body():
+            native = _native.get()
+            native.clip_window(pools[n_pitched_features].cells, pools[n_pitched_features].feats, st['win'][0], st['pitched'], K, C, R,
+                               T * n_beat_fractions * n_pitched_notes, n_pitched_features, stream(dev))
+            if U:
+                native.clip_window(pools[n_unpitched_features].cells, pools[n_unpitched_features].feats, st['win'][1], st['unpitched'],
+                                   K, 1, R, T * n_beat_fractions * n_unpitched_notes, n_unpitched_features, stream(dev))
+            plan.train_iteration(self._flat, gflat, st['pitched'], st['unpitched'], st['losses'], ws=ws)
+
+        # keyed by every address the capture bakes in: the parameters, the gradient buffer and the store's pools (they move
+        # when they grow)
+        key = (self._flat.data_ptr(), gflat.data_ptr()) + tuple(t.data_ptr() for p in pools.values() for t in (p.cells, p.feats))
+        g = st['graph'] if st['key'] == key else None
+        if g is None and st['uses'] >= 1 and dev.type == 'cuda' and getattr(self, 'graph_repeated_shapes', True):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                body()
+            st['graph'], st['key'] = g, key
+        st['uses'] += 1
+        if g is not None:
+            plan._touch(ws)
+            g.replay()
+        else:
+            body()
+        self._publish_grads()
+        return st['losses'].clone()
 
     def static_inputs(self, C, R, T, unpitched=True, lane=0):
         """The note-tensor buffers a captured train_iteration of this shape reads (created on first use by train_iteration): a

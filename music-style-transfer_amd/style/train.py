@@ -15,13 +15,14 @@ them back for the CSV rows, the progress bar and the NaN assertion (which theref
 import csv
 import math
 import os
+import warnings
 
 import numpy as np
 import torch
 
 from style import _native
 from style.data import (iter_inputs, instrument_size, n_instruments, included_instruments, prepare_input,
-                        prepare_input_sparse, get_used_instruments)
+                        prepare_input_sparse, get_used_instruments, SongStore)
 from style.model import (device, get_total_loss, PitchedChannelsEncoder, UnpitchedChannelsEncoder, PitchedRhythmEncoder,
                          UnpitchedRhythmEncoder, StyleEncoder, MelodyEncoder, SongInfoModel, PitchedStyleApplier,
                          UnpitchedStyleApplier, StyleTransferModel)
@@ -69,6 +70,25 @@ def iter_sparse(inputs):
         # pageable memory: this runs beside the loop thread, which captures hipGraphs, and allocating pinned memory is not
         # allowed while a stream captures; train_iteration stages the records through its own pinned slots
         yield prepare_input_sparse(input, max_n_bars, pin=False).drop_silent()
+
+
+def fill_store(inputs, n_songs, store=None):
+    """The next `n_songs` usable songs of `inputs` (items as `train` takes them) into a style.data.SongStore (a new one on the
+    model's device unless given): every song cut to the `800 // C` bars the model would see, songs without pitched notes
+    skipped, silent percussion dropped.  Fewer songs go in when `inputs` runs out."""
+    store = SongStore(device) if store is None else store
+    taken = 0
+    while taken < n_songs:
+        try:
+            input = next(inputs)
+        except StopIteration:
+            break
+        clip = prepare_input_sparse(input, 800 // input[1][1].shape[0], pin=False).drop_silent()
+        if clip is None:
+            continue
+        store.add(clip)
+        taken += 1
+    return store
 
 
 class SmallInputStager:
@@ -205,7 +225,7 @@ def evaluate(model, inputs, n_clips, sparse_input=False):
 def train(model, inputs, n_iterations=5000, iter_size=2, training_info_path='training.csv', save_path='snapshots/',
           save_interval=100, flush_every=20, progress=True, optimizer=None, fused=True, sparse_input=False,
           max_grad_norm=None, skip_nonfinite=False, save_optimizer=False, eval_inputs=None, eval_every=0, eval_clips=8,
-          eval_info_path='validation.csv'):
+          eval_info_path='validation.csv', batch_clips=None, window_bars=16, store_songs=64, window_seed=0):
     """`inputs`: iterator of (filename, get_input(...)) tuples, e.g. iter_parallel(iter_inputs(...)).
     fused=True runs a loop body as ONE C-ABI call (StyleTransferModel.train_iteration: same arithmetic, same gradients, no
     autograd graph); fused=False is the reference's own sequence model(...) -> get_total_loss -> backward.
@@ -223,17 +243,36 @@ def train(model, inputs, n_iterations=5000, iter_size=2, training_info_path='tra
     `eval_clips` songs after every N-th iteration and appends a row to `eval_info_path` (style.metrics.VALIDATION_FIELDS: the
     iteration, the clip count, the averaged loss leaves and the note / song-info metrics of hard_output's decisions); the
     progress meter shows `val_f1`.  Evaluation forms no gradient and leaves the training bits alone; with eval_inputs=None the
-    loop is what it is without this argument."""
+    loop is what it is without this argument.
+    batch_clips = K switches to windowed batches: before the loop the next `store_songs` usable songs of `inputs` (cut to
+    `800 // C` bars as always; songs without pitched notes are skipped, silent percussion is dropped) go into a
+    style.data.SongStore on the device, and every iteration is then `store.sample(rng, K, window_bars)` — K windows of
+    `window_bars` bars of songs of one shape bucket, drawn by numpy.random.default_rng(window_seed) —
+    StyleTransferModel.train_windows (one batched pass over the K windows, cropped on the device) and optimizer.step().  One
+    CSV row per iteration holds the loss leaves averaged over the K clips (on the device).  `iter_size` is ignored with a
+    warning: K takes its place.  Needs fused=True; sparse_input only decides how evaluation rounds upload their songs.
+    batch_clips=None leaves the loop exactly as it is."""
     if optimizer is not None and (max_grad_norm is not None or skip_nonfinite):
         raise ValueError('max_grad_norm / skip_nonfinite configure the default optimizer; with optimizer= set them on that optimizer')
+    windows = None
+    if batch_clips is not None:
+        if not fused:
+            raise ValueError('batch_clips needs fused=True: windowed batches run through StyleTransferModel.train_windows')
+        if int(batch_clips) < 1 or int(window_bars) < 1 or int(store_songs) < 1:
+            raise ValueError('batch_clips, window_bars and store_songs must be at least 1')
+        if iter_size != 1:
+            warnings.warn(f'iter_size={iter_size} is ignored with batch_clips: the optimizer steps after every batch of {batch_clips} clips')
+        windows = (fill_store(inputs, int(store_songs)), np.random.default_rng(window_seed), int(batch_clips), int(window_bars))
+        if not len(windows[0]):
+            raise ValueError('batch_clips: `inputs` held no usable song')
     feeder = None
-    if sparse_input:
+    if sparse_input and windows is None:
         feeder = ParallelIterable(iter_sparse(inputs))
         inputs = iter(feeder)
     try:
         return _train_loop(model, inputs, n_iterations, iter_size, training_info_path, save_path, save_interval, flush_every,
                            progress, optimizer, fused, sparse_input, max_grad_norm, skip_nonfinite, save_optimizer,
-                           eval_inputs if eval_every and eval_every > 0 else None, eval_every, eval_clips, eval_info_path)
+                           eval_inputs if eval_every and eval_every > 0 else None, eval_every, eval_clips, eval_info_path, windows)
     finally:
         if feeder is not None:
             feeder.stop(timeout=5.)
@@ -241,15 +280,26 @@ def train(model, inputs, n_iterations=5000, iter_size=2, training_info_path='tra
 
 def _train_loop(model, inputs, n_iterations, iter_size, training_info_path, save_path, save_interval, flush_every, progress,
                 optimizer, fused, sparse_input, max_grad_norm=None, skip_nonfinite=False, save_optimizer=False,
-                eval_inputs=None, eval_every=0, eval_clips=8, eval_info_path='validation.csv'):
+                eval_inputs=None, eval_every=0, eval_clips=8, eval_info_path='validation.csv', windows=None):
     optimizer = optimizer or FusedAdam(model, lr=.01, step_size=200, gamma=.9, max_grad_norm=max_grad_norm,
                                        skip_nonfinite=skip_nonfinite)
     optimizer.zero_grad()
     pbar = ProgressBar(n_iterations) if progress else None
     log = LossLog(training_info_path, pbar, flush_every, health=getattr(model, 'check_device_status', None),
                   tolerate_nan=bool(getattr(optimizer, 'skip_nonfinite', False)), guard_stats=getattr(optimizer, 'guard_stats', None))
-    stager = SmallInputStager(device) if sparse_input else None
+    stager = SmallInputStager(device) if sparse_input and windows is None else None
     for iteration in range(n_iterations):
+        if windows is not None:
+            store, rng, batch_clips, window_bars = windows
+            batch = store.sample(rng, batch_clips, window_bars)
+            if batch is None:
+                raise ValueError(f'no bucket of the store holds a song with a sounding window of {window_bars} bars')
+            packed = model.train_windows(store, batch).mean(0)      # one row per iteration: the leaves averaged over the K clips
+            log.add(iteration, packed)
+            optimizer.step()                      # K clips have accumulated: K takes iter_size's place
+            _after_iteration(model, optimizer, log, pbar, iteration, eval_inputs, eval_every, eval_clips, eval_info_path,
+                             sparse_input, save_interval, save_path, save_optimizer)
+            continue
         if sparse_input:
             input = next(inputs)
         else:
@@ -279,26 +329,33 @@ def _train_loop(model, inputs, n_iterations, iter_size, training_info_path, save
         log.add(iteration, packed)
         if (iteration + 1) % iter_size == 0:
             optimizer.step()                      # Adam + StepLR + zero_grad in one launch
-        if eval_inputs is not None and (iteration + 1) % eval_every == 0:
-            result = evaluate(model, eval_inputs, eval_clips, sparse_input=sparse_input)
-            if eval_info_path:
-                append_validation_rows(eval_info_path, [validation_row(iteration, result['clips'], result['losses'], result['pitched'],
-                                                                       result['unpitched'], result['song_info'])])
-            if pbar is not None and not math.isnan(result['pitched'].f1):
-                for k in (pbar.values_sum, pbar.values_seen):       # shown as it is (the last round's), not momentum-averaged
-                    k.pop('val_f1', None)
-                pbar.update_values(1, val_f1=result['pitched'].f1)
-        if iteration % save_interval == 0 and save_path:
-            log.flush()
-            path = os.path.join(save_path, f'{iteration}.pkl')
-            assert_dir(path)
-            with open(path, 'wb') as f:
-                torch.save(model, f)
-            if save_optimizer:
-                with open(os.path.join(save_path, f'{iteration}.optim.pkl'), 'wb') as f:
-                    torch.save(optimizer.state_dict(), f)
+        _after_iteration(model, optimizer, log, pbar, iteration, eval_inputs, eval_every, eval_clips, eval_info_path, sparse_input,
+                         save_interval, save_path, save_optimizer)
     log.flush()
     return model
+
+
+def _after_iteration(model, optimizer, log, pbar, iteration, eval_inputs, eval_every, eval_clips, eval_info_path, sparse_input,
+                     save_interval, save_path, save_optimizer):
+    """What follows the optimizer step of an iteration: the evaluation round and the snapshot that are due."""
+    if eval_inputs is not None and (iteration + 1) % eval_every == 0:
+        result = evaluate(model, eval_inputs, eval_clips, sparse_input=sparse_input)
+        if eval_info_path:
+            append_validation_rows(eval_info_path, [validation_row(iteration, result['clips'], result['losses'], result['pitched'],
+                                                                   result['unpitched'], result['song_info'])])
+        if pbar is not None and not math.isnan(result['pitched'].f1):
+            for k in (pbar.values_sum, pbar.values_seen):       # shown as it is (the last round's), not momentum-averaged
+                k.pop('val_f1', None)
+            pbar.update_values(1, val_f1=result['pitched'].f1)
+    if iteration % save_interval == 0 and save_path:
+        log.flush()
+        path = os.path.join(save_path, f'{iteration}.pkl')
+        assert_dir(path)
+        with open(path, 'wb') as f:
+            torch.save(model, f)
+        if save_optimizer:
+            with open(os.path.join(save_path, f'{iteration}.optim.pkl'), 'wb') as f:
+                torch.save(optimizer.state_dict(), f)
 
 
 def split_eval_files(files, n_eval_files):

@@ -2,10 +2,12 @@
 """Drop-in for the reference's train-model.py on the MI355X path: same constants, same loop semantics
 (music-style-transfer_amd/style/train.py), run from the repository root:
 
-    python train-model.py [data_path] [n_eval_files [eval_every]]
+    python train-model.py [--batch-clips K [--window-bars R] [--store-songs N] [--window-seed S]] [data_path] [n_eval_files [eval_every]]
 
 With n_eval_files > 0 the last that many of the sorted files are held out of training and evaluated (forward, loss and note
 metrics, no backward) after every eval_every-th iteration (default 100) into validation.csv.
+With --batch-clips K the loop trains on windowed batches (style.train.train's batch_clips, window_bars, store_songs,
+window_seed): N songs are kept on the device and every iteration is one batched pass over K windows of R bars of them.
 """
 import os
 import sys
@@ -15,8 +17,33 @@ sys.path.insert(0, os.path.join(ROOT, 'music-style-transfer_amd'))
 
 from style.train import main  # noqa: E402
 
+WINDOW_OPTIONS = {'--batch-clips': 'batch_clips', '--window-bars': 'window_bars', '--store-songs': 'store_songs',
+                  '--window-seed': 'window_seed'}
+
+
+def split_options(argv):
+    """(positional arguments, the windowed-batch options as keyword arguments of style.train.train)."""
+    positional, options = [], {}
+    argv = list(argv)
+    while argv:
+        arg = argv.pop(0)
+        if arg in WINDOW_OPTIONS:
+            if not argv:
+                raise SystemExit(f'{arg} needs a value')
+            options[WINDOW_OPTIONS[arg]] = int(argv.pop(0))
+        else:
+            positional.append(arg)
+    if options and 'batch_clips' not in options:
+        raise SystemExit('--window-bars, --store-songs and --window-seed go with --batch-clips')
+    return positional, options
+
+
 if __name__ == '__main__':
-    n_eval_files = int(sys.argv[2]) if len(sys.argv) > 2 else 0
-    held_out = dict(n_eval_files=n_eval_files, eval_every=int(sys.argv[3]) if len(sys.argv) > 3 else 100) if n_eval_files else {}
-    main(*(sys.argv[1:2] or ['data/Lakh MIDI Dataset/clean_midi/']), n_iterations=5000, iter_size=2,
-         training_info_path='training.csv', save_path='snapshots/', save_interval=100, **held_out)
+    args, windows = split_options(sys.argv[1:])
+    n_eval_files = int(args[1]) if len(args) > 1 else 0
+    held_out = dict(n_eval_files=n_eval_files, eval_every=int(args[2]) if len(args) > 2 else 100) if n_eval_files else {}
+    kwargs = dict(n_iterations=5000, iter_size=2, training_info_path='training.csv', save_path='snapshots/', save_interval=100)
+    kwargs.update(held_out)
+    if windows:
+        kwargs.update(windows, iter_size=1)      # K clips accumulate per optimizer step: K takes iter_size's place
+    main(*(args[:1] or ['data/Lakh MIDI Dataset/clean_midi/']), **kwargs)
