@@ -363,6 +363,15 @@ int32_t mst_plan_step_info(const mst_plan* p, int32_t stage_mask, int32_t backwa
  * a carried step's first stage as 0 launches.  mst_plan_time_steps times the GEMM step together with everything it carries and
  * reports a carried step as a row of 0 ms with its own FLOPs / bytes.  Returns the step count. */
 int32_t mst_plan_step_carried(const mst_plan* p, int32_t stage_mask, int32_t backward, int32_t* carried);
+/* The same for every step kind a GEMM launch can carry (gathers, segment reduces, and the combine steps of plans with at most 4
+ * channels): 0 = own launch(es); 1 = the whole step is in its level's GEMM launch (a gather, a one-stage segment reduce, a small
+ * combine site); 2 = the first stage is carried and the second stage is a launch directly behind the carrier (a two-stage segment
+ * reduce, a large combine).  mst_plan_step_carried keeps reporting gathers and segment reduces only.  Returns the step count. */
+int32_t mst_plan_step_riders(const mst_plan* p, int32_t stage_mask, int32_t backward, int32_t* out);
+/* 1 = mst_train_iteration clears the whole-model zero list (mst_zero_grads' ranges, with the LSTM exchange tags) inside its first
+ * forward launch: that launch is a GEMM step of a plan that carries riders, and the plan proved that nothing the launch reads or
+ * writes overlaps a zero chunk.  0 = the zero list is a launch of its own, as in mst_zero_grads. */
+int32_t mst_plan_zero_rides(const mst_plan* p);
 /* (new) instrumentation: the members of GEMM launch step `step` of a pass, one clip's worth, 6 values each:
  * {M, N, K, k-splits, folded rows per clip (0 = not folded), workgroups}.  Returns the member count (<= cap). */
 int32_t mst_plan_step_gemms(const mst_plan* p, int32_t stage_mask, int32_t backward, int32_t step, int32_t* out, int32_t cap);

@@ -7,227 +7,72 @@
 // consumer workgroup (deterministic, no float atomics).  blockIdx.y selects the call site, so
 // independent sites of one dependency level share launches.  HBM/L2-bound: x is read twice per
 // direction, coalesced along the feature axis; the backward reduce reads g once for all channels.
-#include "mst_common.h"
+#include "combine_body.h"
 
-// sums `nv` per-lane values across the 256-lane workgroup; result for value v lands in red[v]
-template <int MC = COMBINE_MAXC>
-__device__ __forceinline__ void block_sum_multi(float* vals, int nv, float (*part)[COMBINE_MAXC + 1], float* red) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int v = 0; v <= MC; ++v) {                 // static indices keep vals[] in registers; nv is workgroup-uniform
-        if (v < nv) {
-            float x = vals[v];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-            if (lane == 0) part[wv][v] = x;
-        }
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < nv) red[threadIdx.x] = (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
-    __syncthreads();
-}
-
-// element e of a rows x cols slice with row stride ld (32-bit index math: a slice has < 2^31 elements)
-__device__ __forceinline__ int64_t elem_off(const CombineDesc& d, int e) {
-    const unsigned r = (unsigned)e / (unsigned)d.cols;
-    return (int64_t)r * d.ld + (int)((unsigned)e - r * (unsigned)d.cols);
-}
-
-// part[blk*(MAXC+1) + c] = partial sum of squares of slice c over this workgroup's elements
-__global__ __launch_bounds__(256) void combine_sumsq_kernel(const CombineDesc* __restrict__ descs, Bases b) {
+// The bodies are in combine_body.h (gemm_kernel runs them too, for the combine steps its launch carries); the kernels here are
+// the stand-alone launches: blockIdx.x = the site's workgroup, blockIdx.y = the site.
+// MC: compile-time bound on the channel count (4: every site of the model up to 4 channels — unrolled loops and shuffle
+// reductions over 32 mostly absent channels were most of the small kernels' ~10 us; 32: the general case)
+// whole_small: a site of at most COMBINE_SMALL elements per slice that shares the two-launch step with larger ones runs its whole
+// step in workgroup 0 of the first launch, on the body the one-launch kernels run (the same sums in the same order, and no partial
+// sums left in scratch, whatever else the site's level holds); 0 for the halves of a tiled plan, whose partial sums meet the
+// other ranks' between the launches
+template <int MC>
+__global__ __launch_bounds__(256) void combine_sumsq_kernel(const CombineDesc* __restrict__ descs, Bases b, int whole_small) {
     const CombineDesc d = descs[blockIdx.y];     // by value: fields stay in registers across barriers
     if ((int)blockIdx.x >= d.nblk) return;
     __shared__ float part[4][COMBINE_MAXC + 1];
     __shared__ float red[COMBINE_MAXC + 1];
-    const float* x = b.p[SP_WS] + d.x_off;
-    const int64_t n = (int64_t)d.rows * d.cols;
-    float acc[COMBINE_MAXC + 1];
-#pragma unroll
-    for (int c = 0; c <= COMBINE_MAXC; ++c) acc[c] = 0.f;
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < (int)n; e += d.nblk * 256) {
-        const int64_t eo = elem_off(d, e);
-#pragma unroll
-        for (int c = 0; c < COMBINE_MAXC; ++c) {
-            if (c < d.Cn) { const float v = x[(int64_t)c * d.cs + eo]; acc[c] = fmaf(v, v, acc[c]); }
-        }
+    if (whole_small && combine_site_small(d)) {
+        if (blockIdx.x == 0) combine_small_fwd_body<MC>(d, threadIdx.x, true, b, part, red);
+        return;
     }
-    block_sum_multi(acc, d.Cn, part, red);
-    if ((int)threadIdx.x < d.Cn) b.p[SP_TMP][d.part_off + blockIdx.x * (COMBINE_MAXC + 1) + threadIdx.x] = red[threadIdx.x];
+    combine_sumsq_body<MC>(d, blockIdx.x, threadIdx.x, true, b, part, red);
 }
 
-// norms from the partials, then out = sum_c x_c n_c / S
-__global__ __launch_bounds__(256) void combine_apply_kernel(const CombineDesc* __restrict__ descs, Bases b) {
-    const CombineDesc d = descs[blockIdx.y];     // by value: fields stay in registers across barriers
-    if ((int)blockIdx.x >= d.nblk) return;
-    __shared__ float nrm[COMBINE_MAXC + 1];
+template <int MC>
+__global__ __launch_bounds__(256) void combine_apply_kernel(const CombineDesc* __restrict__ descs, Bases b, int whole_small) {
+    const CombineDesc d = descs[blockIdx.y];
+    if ((int)blockIdx.x >= d.nblk || (whole_small && combine_site_small(d))) return;
     __shared__ float part[4][COMBINE_MAXC + 1];
     __shared__ float red[COMBINE_MAXC + 1];
-    float* ws = b.p[SP_WS];
-    float* tmp = b.p[SP_TMP];
-    {   // re-sum the per-workgroup partials: lane k takes partial k, then a fixed-order tree (nblk <= 256)
-        float vals[COMBINE_MAXC + 1];
-#pragma unroll
-        for (int c = 0; c <= COMBINE_MAXC; ++c)
-            vals[c] = (c < d.Cn && (int)threadIdx.x < d.nblk) ? tmp[d.part_off + threadIdx.x * (COMBINE_MAXC + 1) + c] : 0.f;
-        block_sum_multi(vals, d.Cn, part, red);
-    }
-    if ((int)threadIdx.x < d.Cn) nrm[threadIdx.x] = sqrtf(1.f + red[threadIdx.x]);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float S = 0.f;
-        for (int c = 0; c < d.Cn; ++c) S += nrm[c];
-        nrm[COMBINE_MAXC] = S;
-    }
-    __syncthreads();
-    if (blockIdx.x == 0 && (int)threadIdx.x <= d.Cn)
-        tmp[d.stats_off + threadIdx.x] = (int)threadIdx.x < d.Cn ? nrm[threadIdx.x] : nrm[COMBINE_MAXC];
-    const float S = nrm[COMBINE_MAXC];
-    const int64_t n = (int64_t)d.rows * d.cols;
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < (int)n; e += d.nblk * 256) {
-        const int64_t eo = elem_off(d, e);
-        float acc = 0.f;
-        for (int c = 0; c < d.Cn; ++c) acc += ws[d.x_off + (int64_t)c * d.cs + eo] * nrm[c];
-        ws[d.out_off + e] = acc / S;
-    }
+    combine_apply_body<MC>(d, blockIdx.x, threadIdx.x, b, part, red);
 }
 
-// part[blk*(MAXC+1) + c] = partial a_c, part[blk*(MAXC+1) + Cn] = partial b
-__global__ __launch_bounds__(256) void combine_bwd_reduce_kernel(const CombineDesc* __restrict__ descs, Bases b) {
-    const CombineDesc d = descs[blockIdx.y];     // by value: fields stay in registers across barriers
+template <int MC>
+__global__ __launch_bounds__(256) void combine_bwd_reduce_kernel(const CombineDesc* __restrict__ descs, Bases b, int whole_small) {
+    const CombineDesc d = descs[blockIdx.y];
     if ((int)blockIdx.x >= d.nblk) return;
+    __shared__ float nc_s[COMBINE_MAXC + 1];
     __shared__ float part[4][COMBINE_MAXC + 1];
     __shared__ float red[COMBINE_MAXC + 1];
-    const float* ws = b.p[SP_WS];
-    const float* gr = b.p[SP_GRAD];
-    const int64_t n = (int64_t)d.rows * d.cols;
-    float acc[COMBINE_MAXC + 1];
-#pragma unroll
-    for (int c = 0; c <= COMBINE_MAXC; ++c) acc[c] = 0.f;
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < (int)n; e += d.nblk * 256) {
-        const int64_t eo = elem_off(d, e);
-        const float g = gr[d.gout_off + e];
-#pragma unroll
-        for (int c = 0; c < COMBINE_MAXC; ++c) {
-            if (c < d.Cn) acc[c] = fmaf(g, ws[d.x_off + (int64_t)c * d.cs + eo], acc[c]);
+    if (whole_small && combine_site_small(d)) {
+        if (blockIdx.x == 0) {
+            if (d.first) combine_small_bwd_body<MC, true>(d, threadIdx.x, true, b, red, nc_s, part);
+            else combine_small_bwd_body<MC, false>(d, threadIdx.x, true, b, red, nc_s, part);
         }
-        acc[COMBINE_MAXC] = fmaf(g, ws[d.out_off + e], acc[COMBINE_MAXC]);
+        return;
     }
-    // move b next to the a_c so one multi-value reduction covers all Cn+1 sums
-    float vals[COMBINE_MAXC + 1];
-#pragma unroll
-    for (int c = 0; c < COMBINE_MAXC; ++c) vals[c] = acc[c];
-    vals[COMBINE_MAXC] = 0.f;
-#pragma unroll
-    for (int c = 0; c <= COMBINE_MAXC; ++c) if (c == d.Cn) vals[c] = acc[COMBINE_MAXC];
-    block_sum_multi(vals, d.Cn + 1, part, red);
-    if ((int)threadIdx.x <= d.Cn) b.p[SP_TMP][d.part_off + blockIdx.x * (COMBINE_MAXC + 1) + threadIdx.x] = red[threadIdx.x];
+    combine_bwd_reduce_body<MC>(d, blockIdx.x, threadIdx.x, true, b, part, red);
 }
 
-__global__ __launch_bounds__(256) void combine_bwd_apply_kernel(const CombineDesc* __restrict__ descs, Bases b) {
-    const CombineDesc d = descs[blockIdx.y];     // by value: fields stay in registers across barriers
-    if ((int)blockIdx.x >= d.nblk) return;
+template <int MC>
+__global__ __launch_bounds__(256) void combine_bwd_apply_kernel(const CombineDesc* __restrict__ descs, Bases b, int whole_small) {
+    const CombineDesc d = descs[blockIdx.y];
+    if ((int)blockIdx.x >= d.nblk || (whole_small && combine_site_small(d))) return;
     __shared__ float coef[COMBINE_MAXC + 1];
     __shared__ float nc_s[COMBINE_MAXC + 1];
-    const float* ws = b.p[SP_WS];
-    float* gr = b.p[SP_GRAD];
-    const float* tmp = b.p[SP_TMP];
     __shared__ float part[4][COMBINE_MAXC + 1];
-    {
-        float vals[COMBINE_MAXC + 1];
-#pragma unroll
-        for (int c = 0; c <= COMBINE_MAXC; ++c)
-            vals[c] = (c <= d.Cn && (int)threadIdx.x < d.nblk) ? tmp[d.part_off + threadIdx.x * (COMBINE_MAXC + 1) + c] : 0.f;
-        block_sum_multi(vals, d.Cn + 1, part, coef);
-    }
-    if ((int)threadIdx.x <= d.Cn) nc_s[threadIdx.x] = tmp[d.stats_off + threadIdx.x];       // n_c ..., S
-    __syncthreads();
-    const float S = nc_s[d.Cn];
-    const float bsum = coef[d.Cn];
-    __shared__ float fa_s[COMBINE_MAXC], fb_s[COMBINE_MAXC];      // per-channel factors: dx_c = g fa_c + fb_c x_c
-    if ((int)threadIdx.x < d.Cn) {
-        const float nc = nc_s[threadIdx.x];
-        fa_s[threadIdx.x] = nc / S; fb_s[threadIdx.x] = ((coef[threadIdx.x] - bsum) / S) / nc;
-    }
-    __syncthreads();
-    const int64_t n = (int64_t)d.rows * d.cols;
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < (int)n; e += d.nblk * 256) {
-        const int64_t eo = elem_off(d, e);
-        const float g = gr[d.gout_off + e];
-        for (int c = 0; c < d.Cn; ++c) {
-            const float x = ws[d.x_off + (int64_t)c * d.cs + eo];
-            float* gx = gr + d.gx_off + (int64_t)c * d.cs + eo;
-            const float v = fmaf(g, fa_s[c], fb_s[c] * x);
-            *gx = d.first ? v : *gx + v;
-        }
-    }
+    if (d.first) combine_bwd_apply_body<MC, true>(d, blockIdx.x, threadIdx.x, b, coef, nc_s, part);
+    else combine_bwd_apply_body<MC, false>(d, blockIdx.x, threadIdx.x, b, coef, nc_s, part);
 }
 
-// Small sites (<= COMBINE_SMALL elements per slice: the per-bar tensors, the style vector) need no cross-workgroup
-// re-sum: one workgroup per site does reduction and elementwise pass in ONE launch instead of two.
-// MC: compile-time bound on the channel count (4: every site of the model up to 4 channels — unrolled loops and shuffle
-// reductions over 32 mostly absent channels were most of these kernels' ~10 us; 32: the general case)
 template <int MC>
 __global__ __launch_bounds__(256) void combine_small_fwd_kernel(const CombineDesc* __restrict__ descs, Bases b) {
     const CombineDesc d = descs[blockIdx.x];
-    __shared__ float nrm[COMBINE_MAXC + 1];
     __shared__ float part[4][COMBINE_MAXC + 1];
     __shared__ float red[COMBINE_MAXC + 1];
-    float* ws = b.p[SP_WS];
-    float* tmp = b.p[SP_TMP];
-    const int n = d.rows * d.cols;
-    float acc[MC + 1];
-#pragma unroll
-    for (int c = 0; c <= MC; ++c) acc[c] = 0.f;
-    // U elements per lane and trip, all their loads issued before the first use: one workgroup walks the whole site, and a
-    // trip per element was a chain of n / 256 dependent L2 round trips (16 us for 4096 elements).  Per lane the elements
-    // are still accumulated in ascending order.
-    constexpr int U = MC <= 4 ? 4 : 1;
-    for (int e0 = threadIdx.x; e0 < n; e0 += 256 * U) {
-        float v[U][MC];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int e = e0 + 256 * u;
-            const bool ok = e < n;
-            const int64_t eo = elem_off(d, ok ? e : 0);
-#pragma unroll
-            for (int c = 0; c < MC; ++c) v[u][c] = (ok && c < d.Cn) ? ws[d.x_off + (int64_t)c * d.cs + eo] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-#pragma unroll
-            for (int c = 0; c < MC; ++c) acc[c] = fmaf(v[u][c], v[u][c], acc[c]);
-        }
-    }
-    block_sum_multi<MC>(acc, d.Cn, part, red);
-    if ((int)threadIdx.x < d.Cn) nrm[threadIdx.x] = sqrtf(1.f + red[threadIdx.x]);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float S = 0.f;
-        for (int c = 0; c < d.Cn; ++c) S += nrm[c];
-        nrm[COMBINE_MAXC] = S;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x <= d.Cn) tmp[d.stats_off + threadIdx.x] = (int)threadIdx.x < d.Cn ? nrm[threadIdx.x] : nrm[COMBINE_MAXC];
-    const float S = nrm[COMBINE_MAXC];
-    for (int e0 = threadIdx.x; e0 < n; e0 += 256 * U) {
-        float v[U][MC];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int e = e0 + 256 * u;
-            const bool ok = e < n;
-            const int64_t eo = elem_off(d, ok ? e : 0);
-#pragma unroll
-            for (int c = 0; c < MC; ++c) v[u][c] = (ok && c < d.Cn) ? ws[d.x_off + (int64_t)c * d.cs + eo] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int e = e0 + 256 * u;
-            float a = 0.f;
-#pragma unroll
-            for (int c = 0; c < MC; ++c) if (c < d.Cn) a += v[u][c] * nrm[c];
-            if (e < n) ws[d.out_off + e] = a / S;
-        }
-    }
+    combine_small_fwd_body<MC>(d, threadIdx.x, true, b, part, red);
 }
 
 template <int MC>
@@ -236,117 +81,44 @@ __global__ __launch_bounds__(256) void combine_small_bwd_kernel(const CombineDes
     __shared__ float coef[COMBINE_MAXC + 1];
     __shared__ float nc_s[COMBINE_MAXC + 1];
     __shared__ float part[4][COMBINE_MAXC + 1];
-    const float* ws = b.p[SP_WS];
-    float* gr = b.p[SP_GRAD];
-    const float* tmp = b.p[SP_TMP];
-    const int n = d.rows * d.cols;
-    float acc[MC + 1];
-#pragma unroll
-    for (int c = 0; c <= MC; ++c) acc[c] = 0.f;
-    constexpr int U = MC <= 4 ? 4 : 1;                 // loads of U elements in flight per trip (see combine_small_fwd_kernel)
-    for (int e0 = threadIdx.x; e0 < n; e0 += 256 * U) {
-        float v[U][MC], g[U], o[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int e = e0 + 256 * u;
-            const bool ok = e < n;
-            const int64_t eo = elem_off(d, ok ? e : 0);
-            g[u] = ok ? gr[d.gout_off + e] : 0.f;
-            o[u] = ok ? ws[d.out_off + e] : 0.f;
-#pragma unroll
-            for (int c = 0; c < MC; ++c) v[u][c] = (ok && c < d.Cn) ? ws[d.x_off + (int64_t)c * d.cs + eo] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (e0 + 256 * u < n) {
-#pragma unroll
-                for (int c = 0; c < MC; ++c) if (c < d.Cn) acc[c] = fmaf(g[u], v[u][c], acc[c]);
-                acc[MC] = fmaf(g[u], o[u], acc[MC]);
-            }
-        }
-    }
-    float vals[MC + 1];
-#pragma unroll
-    for (int c = 0; c < MC; ++c) vals[c] = acc[c];
-    vals[MC] = 0.f;
-#pragma unroll
-    for (int c = 0; c <= MC; ++c) if (c == d.Cn) vals[c] = acc[MC];
-    block_sum_multi<MC>(vals, d.Cn + 1, part, coef);
-    if ((int)threadIdx.x <= d.Cn) nc_s[threadIdx.x] = tmp[d.stats_off + threadIdx.x];       // n_c ..., S
-    __syncthreads();
-    const float S = nc_s[d.Cn];
-    const float bsum = coef[d.Cn];
-    // per-channel factors once per lane (two IEEE divisions per element and channel were most of the elementwise pass):
-    // dx_c = g n_c / S + ((b_c - b) / S) x_c / n_c
-    float fa[MC], fb[MC];
-#pragma unroll
-    for (int c = 0; c < MC; ++c) {
-        const float nc = c < d.Cn ? nc_s[c] : 1.f;
-        fa[c] = nc / S; fb[c] = c < d.Cn ? ((coef[c] - bsum) / S) / nc : 0.f;
-    }
-    for (int e0 = threadIdx.x; e0 < n; e0 += 256 * U) {
-        float x[U][MC], old[U][MC], g[U];
-        int64_t eo[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int e = e0 + 256 * u;
-            const bool ok = e < n;
-            eo[u] = elem_off(d, ok ? e : 0);
-            g[u] = ok ? gr[d.gout_off + e] : 0.f;
-#pragma unroll
-            for (int c = 0; c < MC; ++c) {
-                const bool okc = ok && c < d.Cn;
-                x[u][c] = okc ? ws[d.x_off + (int64_t)c * d.cs + eo[u]] : 0.f;
-                old[u][c] = (okc && !d.first) ? gr[d.gx_off + (int64_t)c * d.cs + eo[u]] : 0.f;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (e0 + 256 * u < n) {
-#pragma unroll
-                for (int c = 0; c < MC; ++c) {
-                    if (c < d.Cn) {
-                        const float v = fmaf(g[u], fa[c], fb[c] * x[u][c]);
-                        gr[d.gx_off + (int64_t)c * d.cs + eo[u]] = d.first ? v : old[u][c] + v;
-                    }
-                }
-            }
-        }
-    }
+    if (d.first) combine_small_bwd_body<MC, true>(d, threadIdx.x, true, b, coef, nc_s, part);
+    else combine_small_bwd_body<MC, false>(d, threadIdx.x, true, b, coef, nc_s, part);
 }
 
 // all_small: every site of the (merged) launch has <= COMBINE_SMALL elements per slice (2: and at most 4 channels)
-int launch_combine_fwd(const CombineDesc* dev, int count, int max_nblk, int all_small, Bases b, hipStream_t s) {
+// mc4: no site of the plan has more than 4 channels (the large kernels' MC = 4 flavour)
+int launch_combine_fwd(const CombineDesc* dev, int count, int max_nblk, int all_small, int mc4, Bases b, hipStream_t s) {
     if (count <= 0) return 0;
     if (all_small) {
         if (all_small == 2) hipLaunchKernelGGL(combine_small_fwd_kernel<4>, dim3(count), dim3(256), 0, s, dev, b);
         else hipLaunchKernelGGL(combine_small_fwd_kernel<COMBINE_MAXC>, dim3(count), dim3(256), 0, s, dev, b);
         return (int)hipGetLastError();
     }
-    hipLaunchKernelGGL(combine_sumsq_kernel, dim3(max_nblk, count), dim3(256), 0, s, dev, b);
-    hipLaunchKernelGGL(combine_apply_kernel, dim3(max_nblk, count), dim3(256), 0, s, dev, b);
-    return (int)hipGetLastError();
+    if (int e = launch_combine_phase(dev, max_nblk, 0, b, s, count, mc4, 1)) return e;
+    return launch_combine_phase(dev, max_nblk, 1, b, s, count, mc4, 1);
 }
 
-int launch_combine_bwd(const CombineDesc* dev, int count, int max_nblk, int all_small, Bases b, hipStream_t s) {
+int launch_combine_bwd(const CombineDesc* dev, int count, int max_nblk, int all_small, int mc4, Bases b, hipStream_t s) {
     if (count <= 0) return 0;
     if (all_small) {
         if (all_small == 2) hipLaunchKernelGGL(combine_small_bwd_kernel<4>, dim3(count), dim3(256), 0, s, dev, b);
         else hipLaunchKernelGGL(combine_small_bwd_kernel<COMBINE_MAXC>, dim3(count), dim3(256), 0, s, dev, b);
         return (int)hipGetLastError();
     }
-    hipLaunchKernelGGL(combine_bwd_reduce_kernel, dim3(max_nblk, count), dim3(256), 0, s, dev, b);
-    hipLaunchKernelGGL(combine_bwd_apply_kernel, dim3(max_nblk, count), dim3(256), 0, s, dev, b);
-    return (int)hipGetLastError();
+    if (int e = launch_combine_phase(dev, max_nblk, 2, b, s, count, mc4, 1)) return e;
+    return launch_combine_phase(dev, max_nblk, 3, b, s, count, mc4, 1);
 }
 
 // ---- tiled plans: the halves of a combine on their own (the ranks' partial sums meet in between), strided row copies
 // and the fold / spread pair around an exchange (mst_common.h)
-int launch_combine_phase(const CombineDesc* dev, int nblk, int which, Bases b, hipStream_t s) {
-    if (which == 0) hipLaunchKernelGGL(combine_sumsq_kernel, dim3(nblk, 1), dim3(256), 0, s, dev, b);
-    else if (which == 1) hipLaunchKernelGGL(combine_apply_kernel, dim3(nblk, 1), dim3(256), 0, s, dev, b);
-    else if (which == 2) hipLaunchKernelGGL(combine_bwd_reduce_kernel, dim3(nblk, 1), dim3(256), 0, s, dev, b);
-    else hipLaunchKernelGGL(combine_bwd_apply_kernel, dim3(nblk, 1), dim3(256), 0, s, dev, b);
+int launch_combine_phase(const CombineDesc* dev, int nblk, int which, Bases b, hipStream_t s, int count, int mc4, int whole_small) {
+    const dim3 grid(nblk, count), lanes(256);
+#define COMBINE_PHASE(K) do { if (mc4) hipLaunchKernelGGL(K<4>, grid, lanes, 0, s, dev, b, whole_small); else hipLaunchKernelGGL(K<COMBINE_MAXC>, grid, lanes, 0, s, dev, b, whole_small); } while (0)
+    if (which == 0) COMBINE_PHASE(combine_sumsq_kernel);
+    else if (which == 1) COMBINE_PHASE(combine_apply_kernel);
+    else if (which == 2) COMBINE_PHASE(combine_bwd_reduce_kernel);
+    else COMBINE_PHASE(combine_bwd_apply_kernel);
+#undef COMBINE_PHASE
     return (int)hipGetLastError();
 }
 

@@ -18,7 +18,7 @@
 // Independent GEMMs share one launch: the 1-D grid is the concatenation of every member's
 // (tile, k-split) workgroups; k-splits of weight gradients write deterministic slabs that are
 // reduced later in order.
-#include "mst_common.h"
+#include "combine_body.h"
 
 __device__ __forceinline__ float act_fwd(int act, float z, int col) {
     if (act == ACT_LEAKY) return z > 0.f ? z : z * LEAKY;
@@ -720,6 +720,30 @@ int gemm_blocks(const GemmDesc& g, int mfma) {
     return ((ntile + run - 1) / run) * g.ksplit;
 }
 
+// A combine step carried by a gemm_kernel launch (the MC = 4 flavour only: the general one needs more registers than a
+// 1024-lane workgroup has).  Small site: the whole step, run by the block's first 256 lanes; the others neither load nor store.
+// Large site: block `cb` runs groups 4 cb .. 4 cb + 3 of the site's nblk, each with its own LDS slices; group g writes the partial
+// that workgroup g of the stand-alone kernel writes.
+__device__ __forceinline__ void combine_rider(const CombineDesc d, const int cb, int kind, const Bases& b, float* smem) {
+    constexpr int ROW = COMBINE_MAXC + 1;
+    const int tid = threadIdx.x;
+    if ((kind == COMB_RIDE_SUMSQ || kind == COMB_RIDE_REDUCE) && combine_site_small(d)) {
+        if (cb != 0) return;            // a small site among a step's large ones: its whole step, in the site's first block
+        kind = kind == COMB_RIDE_SUMSQ ? COMB_RIDE_SMALL_F : COMB_RIDE_SMALL_B;
+    }
+    if (kind == COMB_RIDE_SMALL_F) {
+        combine_small_fwd_body<4>(d, tid, tid < 256, b, reinterpret_cast<float (*)[ROW]>(smem), smem + 4 * ROW);
+    } else if (kind == COMB_RIDE_SMALL_B) {
+        if (d.first) combine_small_bwd_body<4, true>(d, tid, tid < 256, b, smem, smem + ROW, reinterpret_cast<float (*)[ROW]>(smem + 2 * ROW));
+        else combine_small_bwd_body<4, false>(d, tid, tid < 256, b, smem, smem + ROW, reinterpret_cast<float (*)[ROW]>(smem + 2 * ROW));
+    } else {
+        const int gi = tid >> 8, grp = cb * 4 + gi;
+        float* slice = smem + gi * 5 * ROW;
+        if (kind == COMB_RIDE_SUMSQ) combine_sumsq_body<4>(d, grp, tid & 255, grp < d.nblk, b, reinterpret_cast<float (*)[ROW]>(slice), slice + 4 * ROW);
+        else combine_bwd_reduce_body<4>(d, grp, tid & 255, grp < d.nblk, b, reinterpret_cast<float (*)[ROW]>(slice), slice + 4 * ROW);
+    }
+}
+
 template <int WV> __device__ __forceinline__ void gather_rows(const GatherDesc& d, const int blk, const int nblk, const Bases& b);
 __device__ __forceinline__ void segred_group(const SegRedDesc* __restrict__ descs, const int members, const int clip, const int lb, const int t, const Bases& b);
 
@@ -727,19 +751,26 @@ __device__ __forceinline__ void segred_group(const SegRedDesc* __restrict__ desc
 // (workgroup-uniform) variant picks the instantiation.  That lets the scheduler put *independent*
 // GEMMs of different kinds — e.g. the weight-gradient and input-gradient GEMMs of one layer, or
 // all small Linears of one dependency level — into a single launch.
-// The launch also carries its level's gathers and stage-1 segment reduces (GemmRiders): a clip's block range starts with the
-// segment-reduce blocks (the longest walk of the three, so dispatched first: four of segred_kernel's 256-lane groups each), then
-// the gather blocks (sixteen rows each, one per wave), then the GEMM members' tiles.  Rider blocks touch no LDS and meet no barrier.
-__global__ __launch_bounds__(GEMM_THREADS) void gemm_kernel(const GemmDesc* __restrict__ descs, const int* __restrict__ owner, int count, int blocks_per_clip, Bases b, GemmRiders r) {
-    // A tile | B tile; the final reduce overlays the whole block with one 32x32 partial tile per wave
-    constexpr int TILE_F = GEMM_BK * (GEMM_BM + GEMM_PAD), RED_F = (GEMM_THREADS / 64) * GEMM_BM * GEMM_BN;
-    __shared__ float smem[(2 * TILE_F > RED_F) ? 2 * TILE_F : RED_F];
-    float (*As)[GEMM_BM + GEMM_PAD] = reinterpret_cast<float (*)[GEMM_BM + GEMM_PAD]>(smem);
-    float (*Bs)[GEMM_BN + GEMM_PAD] = reinterpret_cast<float (*)[GEMM_BN + GEMM_PAD]>(smem + TILE_F);
-    // flat 1-D grid: clip-major; inside a clip's block range, behind the riders, member y owns [blk_begin, blk_begin + tiles * ksplit)
-    const int clip = blockIdx.x / blocks_per_clip;
-    int lb = blockIdx.x - clip * blocks_per_clip;
+// The launch also carries its level's combine steps, gathers and stage-1 segment reduces (GemmRiders): a clip's block range starts
+// with the combine blocks (two passes over a site around a reduction: the longest walk, so dispatched first), then the
+// segment-reduce blocks (four of segred_kernel's 256-lane groups each), then the gather blocks (sixteen rows each, one per wave),
+// then the zero list's chunks (a train iteration's first forward launch; the shortest walk), then the GEMM members' tiles.
+// Segment-reduce, gather and zero blocks touch no LDS and meet no barrier; a combine block's few hundred bytes of LDS overlay
+// smem, and every lane of it reaches every barrier.  No workgroup waits for another one.
+// block `lb` of a clip's rider blocks
+__device__ __forceinline__ void gemm_rider_block(const GemmRiders& r, const int clip, int lb, const Bases& b, float* smem) {
     const int seg_blocks = (r.seg_groups + 3) >> 2, gat_blocks = r.gat_members * r.gat_blocks;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const GemmRiders::Comb& cr = r.comb[q];
+        const int comb_blocks = cr.sites * cr.blocks;
+        if (lb < comb_blocks) {
+            const int m = lb / cr.blocks;
+            combine_rider(cr.descs[clip * cr.sites + m], lb - m * cr.blocks, cr.kind, b, smem);
+            return;
+        }
+        lb -= comb_blocks;
+    }
     if (lb < seg_blocks) {
         const int grp = lb * 4 + (threadIdx.x >> 8);
         if (grp < r.seg_groups) segred_group(r.segreds, r.seg_members, clip, grp, threadIdx.x & 255, b);
@@ -752,6 +783,29 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_kernel(const GemmDesc* __re
         return;
     }
     lb -= gat_blocks;
+    if (lb < r.zero_chunks) {
+        const ZeroChunk c = r.zero[lb];
+        float* p = b.p[SP_GRAD] + (int64_t)clip * r.zero_stride + c.off;
+        for (int i = threadIdx.x; i < c.len; i += GEMM_THREADS) p[i] = 0.f;
+    }
+}
+
+// rider_blocks: gemm_rider_blocks(r), as an argument of its own next to blocks_per_clip: a tile workgroup decides with the first
+// batch of kernel-argument loads that it is one, and never waits for a field of `r`
+__global__ __launch_bounds__(GEMM_THREADS) void gemm_kernel(const GemmDesc* __restrict__ descs, const int* __restrict__ owner, int count, int blocks_per_clip, int rider_blocks, Bases b, GemmRiders r) {
+    // A tile | B tile; the final reduce overlays the whole block with one 32x32 partial tile per wave
+    constexpr int TILE_F = GEMM_BK * (GEMM_BM + GEMM_PAD), RED_F = (GEMM_THREADS / 64) * GEMM_BM * GEMM_BN;
+    __shared__ float smem[(2 * TILE_F > RED_F) ? 2 * TILE_F : RED_F];
+    float (*As)[GEMM_BM + GEMM_PAD] = reinterpret_cast<float (*)[GEMM_BM + GEMM_PAD]>(smem);
+    float (*Bs)[GEMM_BN + GEMM_PAD] = reinterpret_cast<float (*)[GEMM_BN + GEMM_PAD]>(smem + TILE_F);
+    // flat 1-D grid: clip-major; inside a clip's block range, behind the riders, member y owns [blk_begin, blk_begin + tiles * ksplit)
+    const int clip = blockIdx.x / blocks_per_clip;
+    int lb = blockIdx.x - clip * blocks_per_clip;
+    if (lb < rider_blocks) {
+        gemm_rider_block(r, clip, lb, b, smem);
+        return;
+    }
+    lb -= rider_blocks;
     const int lo = owner[lb];                        // member of this block: one uniform load (the plan's block -> member table)
     const GemmDesc d = descs[clip * count + lo];     // by value (scalar loads once): a reference would be re-read after every barrier
     const int local = lb - d.blk_begin;
@@ -790,7 +844,7 @@ int gemm_variant(const GemmDesc& g) {
     return -1;
 }
 
-int gemm_rider_blocks(const GemmRiders& r) { return (r.seg_groups + 3) / 4 + r.gat_members * r.gat_blocks; }
+int gemm_rider_blocks(const GemmRiders& r) { return r.comb[0].sites * r.comb[0].blocks + r.comb[1].sites * r.comb[1].blocks + (r.seg_groups + 3) / 4 + r.gat_members * r.gat_blocks + r.zero_chunks; }
 
 int launch_gemm(const GemmDesc* dev_descs, const int* dev_owner, int members, int blocks_per_clip, int clips, int mfma, Bases b, hipStream_t s, const GemmRiders* riders) {
     if (members <= 0 || blocks_per_clip <= 0 || clips <= 0) return 0;
@@ -798,7 +852,7 @@ int launch_gemm(const GemmDesc* dev_descs, const int* dev_owner, int members, in
     if (mfma && gemm_rider_blocks(r)) return (int)hipErrorInvalidValue;        // only the 32x32 kernel carries riders
     blocks_per_clip += gemm_rider_blocks(r);
     if (mfma) hipLaunchKernelGGL(gemm_mfma_kernel, dim3(blocks_per_clip * clips), dim3(MF_THREADS), 0, s, dev_descs, dev_owner, members, blocks_per_clip, b);
-    else hipLaunchKernelGGL(gemm_kernel, dim3(blocks_per_clip * clips), dim3(GEMM_THREADS), 0, s, dev_descs, dev_owner, members, blocks_per_clip, b, r);
+    else hipLaunchKernelGGL(gemm_kernel, dim3(blocks_per_clip * clips), dim3(GEMM_THREADS), 0, s, dev_descs, dev_owner, members, blocks_per_clip, gemm_rider_blocks(r), b, r);
     return (int)hipGetLastError();
 }
 

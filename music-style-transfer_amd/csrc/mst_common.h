@@ -162,11 +162,20 @@ struct SegRedDesc {
     int64_t y_off;
 };
 
-// ---- riders of a gemm_kernel launch: the gathers and stage-1 segment reduces of the GEMMs' dependency level, in the same grid.
-// Both tables are clips x members (clip-major), the ones a stand-alone gather_kernel / segred_kernel launch would be given.
+// ---- riders of a gemm_kernel launch: the gathers, stage-1 segment reduces and combine steps of the GEMMs' dependency level, in
+// the same grid, and (first forward launch of a train iteration) the gradient arena's zero list.
+// The tables are clips x members (clip-major), the ones a stand-alone gather_kernel / segred_kernel / combine launch would be given.
+struct CombineDesc;
+struct ZeroChunk;
+enum { COMB_RIDE_NONE = 0, COMB_RIDE_SMALL_F, COMB_RIDE_SMALL_B, COMB_RIDE_SUMSQ, COMB_RIDE_REDUCE };
 struct GemmRiders {
     const SegRedDesc* segreds; int32_t seg_members, seg_groups;    // seg_groups: 256-lane groups per clip (segred_kernel's blocks_per_clip)
     const GatherDesc* gathers; int32_t gat_members, gat_blocks;    // gat_blocks: workgroups of GATHER_RIDER_ROWS rows per member
+    // combine sites of at most 4 channels: a small site's whole step in one workgroup (its first 256 lanes), or a large site's
+    // first phase, four of its 256-lane groups per workgroup (the second phase is a launch behind this one)
+    // (a level has at most one step of small and one of large sites per pass: two slots)
+    struct Comb { const CombineDesc* descs; int32_t sites, blocks, kind; } comb[2];     // sites per clip, workgroups per site, COMB_RIDE_*
+    const ZeroChunk* zero; int32_t zero_chunks; int64_t zero_stride;          // chunks per clip (one workgroup each), floats between two clips' gradient slices
 };
 
 // ---- LSTM recurrence
@@ -319,8 +328,10 @@ struct CopyDesc { int64_t src_off, dst_off; int32_t na, nb, cols, src_sa, src_sb
 struct FoldDesc { int32_t space, nrows, row_stride, ncols, col_stride, pad; int64_t part_off, sum_off /* SP_TMP */; };
 int launch_copy_rows(const CopyDesc* dev, const CopyDesc& host, int backward, Bases b, hipStream_t s);
 int launch_fold(const FoldDesc* dev, int spread, Bases b, hipStream_t s);
-// one half of a two-launch combine: which = 0 sums of squares, 1 apply, 2 backward reduce, 3 backward apply
-int launch_combine_phase(const CombineDesc* dev, int nblk, int which, Bases b, hipStream_t s);
+// one half of a two-launch combine over `count` sites: which = 0 sums of squares, 1 apply, 2 backward reduce, 3 backward apply
+// mc4: no site has more than 4 channels; whole_small: the halves of a step of a one-rank plan — a small site among the sites does
+// its whole step in the first half (combine.hip)
+int launch_combine_phase(const CombineDesc* dev, int nblk, int which, Bases b, hipStream_t s, int count = 1, int mc4 = 0, int whole_small = 0);
 
 // ---- deferred weight-gradient reduction: gpar[dst+i] += sum_s ws[src + s*stride + i]
 // (reps = clips of a batched plan: clip r's slabs sit rep_stride floats after clip r-1's; summed clip-major, in order)
@@ -368,8 +379,8 @@ int launch_lstm_transpose(const LstmDesc* dev_descs, int count, int maxH, int mu
 int launch_lstm_fwd(const LstmDesc* dev_descs, int count, int maxB, int maxH, int multi, Bases b, hipStream_t s);
 int launch_lstm_bwd(const LstmDesc* dev_descs, int count, int maxB, int maxH, int multi, Bases b, hipStream_t s);
 int lstm_multi_blocks_per_cu();      // workgroups of the multi-workgroup LSTM kernels one CU holds at once (occupancy API)
-int launch_combine_fwd(const CombineDesc* dev_descs, int count, int max_nblk, int all_small, Bases b, hipStream_t s);
-int launch_combine_bwd(const CombineDesc* dev_descs, int count, int max_nblk, int all_small, Bases b, hipStream_t s);
+int launch_combine_fwd(const CombineDesc* dev_descs, int count, int max_nblk, int all_small, int mc4, Bases b, hipStream_t s);
+int launch_combine_bwd(const CombineDesc* dev_descs, int count, int max_nblk, int all_small, int mc4, Bases b, hipStream_t s);
 // `count` descriptors of identical shape (the clips of a batched plan), blockIdx.y = descriptor
 int launch_me_sumsq(const NotesDesc* dev, const NotesDesc& host, int count, Bases b, hipStream_t s);
 int launch_me_notes_fwd(const NotesDesc* dev, const NotesDesc& host, int count, Bases b, hipStream_t s);

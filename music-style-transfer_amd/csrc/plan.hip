@@ -248,12 +248,15 @@ template <class D> struct DescTable {
 
 // What a K_GEMM launch carries besides its members (mst_plan::mixes): its level's K_SEGRED step (first scheduled descriptor, members and
 // 256-lane groups per clip, stage-2 blocks) and K_GATHER step (first descriptor, members per clip, most rows of a member)
-struct Riders { int seg_first = 0, seg_members = 0, seg_groups = 0, seg_stage2 = 0, gat_first = 0, gat_members = 0, gat_rows = 0; };
+// and K_COMB_F / K_COMB_B steps (slot 0: small sites, slot 1: large sites, whose second phase is a launch behind the carrier;
+// first descriptor, sites per clip, most workgroups of a site, the pass)
+struct CombRide { int first = 0, sites = 0, nblk = 0, bwd = 0; };
+struct Riders { int seg_first = 0, seg_members = 0, seg_groups = 0, seg_stage2 = 0, gat_first = 0, gat_members = 0, gat_rows = 0; CombRide comb[2]; };
 struct Step { int kind, first, count, a, b, stage; int c = 0; int lvl = 0; int chain = -1; int signal = -1; int wait[3] = {-1, -1, -1};
               int carried = 0; Riders ride; };
 // c: GEMM steps — offset of the step's block -> member table; lvl: dependency level in its scheduled pass; chain / signal / wait: the stream the
 // launch goes to, the event slot recorded behind it and the slots its stream waits for in front of it (assign_streams; chain -1 = caller's stream)
-// carried: a gather / segment-reduce step that stays in the list (dependencies, first-writer flags, instrumentation) but is launched by
+// carried: a gather / segment-reduce / combine step that stays in the list (dependencies, first-writer flags, instrumentation) but is launched by
 // the K_GEMM step of its level, whose `ride` names its descriptors
 struct Acc { int space; int64_t lo, hi; bool w; bool accum = false, dense = true; };   // accum: a += writer; dense: covers [lo, hi) fully
 struct Op { int stage; std::vector<Step> fwd, bwd; };
@@ -293,12 +296,18 @@ struct mst_plan {
     bool tiled() const { return opt.tile_rows > 0; }
     // a level's gathers and segment reduces ride on its GEMM launch: the one-stream, merged plans on the 32x32 tiling only
     bool mixes() const { return !mfma && !tiled() && opt.branches != 1 && !opt.no_merge; }
+    // the combine kernels' compile-time channel bound: 4 where no site can have more channels, COMBINE_MAXC otherwise
+    int mc4() const { return d.C <= 4 ? 1 : 0; }
     int Rl() const { return tiled() ? opt.tile_rows : d.R; }
     int P() const { return d.C * Rl() * d.T; }          // positions / beats this plan computes (all of them when not tiled)
     int Q() const { return Rl() * d.T; }
     struct Xchg { int space; int64_t off; int32_t len; };
     std::vector<Xchg> xchgs;
     bool tags_in_zero = false;             // zero_all also clears the multi-workgroup LSTM's exchange tags
+    // step of sched_all[0] whose launch clears zero_all in mst_train_iteration (-1: mst_zero_grads is launched): the pass's first
+    // launch, if it is a K_GEMM step that carries riders and neither it nor a step it carries touches a zero chunk
+    int zero_ride = -1;
+    void find_zero_ride();
     std::vector<ZeroChunk> zero_fwd; ZeroChunk* d_zero_fwd = nullptr;      // activation ranges cleared before a tiled forward
     int64_t loss_sum_off = 0;                                               // [SP_TMP] 16 floats: the loss partial sums, folded
     int loss_fold[2] = {-1, -1};
@@ -1515,15 +1524,19 @@ void mst_plan::schedule_pass(const std::vector<Step>& seq, std::vector<Step>& ou
         }
         // Steps of one level are independent, so the level's gather and segment-reduce launches (stage 1) ride on its GEMM launch
         // (of the same stage where stages may run separately).  The carried steps stay in the list; run_step skips them.
+        // So do its combine steps where no site has more than 4 channels (the flavour whose registers fit gemm_kernel): a small
+        // site's whole step, a large site's first phase.
         if (!mixes()) continue;
         for (size_t e = lv_begin; e < out.size(); ++e) {
-            if (out[e].kind != K_GATHER && out[e].kind != K_SEGRED) continue;
+            const bool comb = (out[e].kind == K_COMB_F || out[e].kind == K_COMB_B) && mc4();
+            if (out[e].kind != K_GATHER && out[e].kind != K_SEGRED && !comb) continue;
             for (size_t c = lv_begin; c < out.size(); ++c) {
                 Step& g = out[c];
                 if (g.kind != K_GEMM || (!across_stages && g.stage != out[e].stage)) continue;
                 const Step& s = out[e];
                 if (s.kind == K_GATHER && !g.ride.gat_members) { g.ride.gat_first = s.first; g.ride.gat_members = s.count / K(); g.ride.gat_rows = s.a; }
                 else if (s.kind == K_SEGRED && !g.ride.seg_members) { g.ride.seg_first = s.first; g.ride.seg_members = s.count / K(); g.ride.seg_groups = s.a; g.ride.seg_stage2 = s.b; }
+                else if (comb && !g.ride.comb[s.b != 0].sites) g.ride.comb[s.b != 0] = CombRide{s.first, s.count / K(), s.a, s.kind == K_COMB_B};
                 else continue;
                 out[e].carried = 1;
                 break;
@@ -1695,6 +1708,7 @@ void mst_plan::schedule() {
     if (K() == 1)
         for (const LstmDesc& l : lstms.host)
             if (l.multi) { zero_all.push_back(ZeroChunk{act_top + l.xch_off, (int32_t)(2 * (2 * l.H + 8 * l.H)), 0}); tags_in_zero = true; }
+    find_zero_ride();
     if (!tiled()) return;
     // ---- one train iteration of a tiled plan as phases that end at an exchange
     {   // loss partial sums (7 per note tensor, one row per workgroup) -> 16 floats that the ranks sum
@@ -1745,6 +1759,34 @@ void mst_plan::schedule() {
     { Phase ph = mk(1, 0, 0, 0); ph.nx = 1; ph.xchg[0] = lx; phases.push_back(ph); }
     phases.push_back(mk(2, 0, 0, 0));
     split(1);
+}
+
+void mst_plan::find_zero_ride() {
+    zero_ride = -1;
+    if (!mixes() || zero_all.empty()) return;
+    const std::vector<Step>& L = sched_all[0];
+    int first = -1;
+    for (int i = 0; i < (int)L.size() && first < 0; ++i) {
+        if (L[i].carried) continue;
+        if (tags_in_zero && L[i].kind == K_LSTM_T && lstms.sched[L[i].first].multi) continue;      // skipped: its only job was the clear
+        first = i;
+    }
+    if (first < 0 || L[first].kind != K_GEMM) return;
+    // everything in absolute workspace floats: activations, then the gradient arena, then the scratch arena (make_bases)
+    auto base = [&](int space) -> int64_t { return space == SP_WS ? 0 : space == SP_GRAD ? (int64_t)K() * act_top : space == SP_TMP ? 2 * (int64_t)K() * act_top : -1; };
+    std::vector<Acc> acc;
+    accesses(L[first], acc, true);
+    for (const Step& s : L) if (s.carried && s.lvl == L[first].lvl) accesses(s, acc, true);      // (a superset of what the launch carries)
+    for (const Acc& a : acc) {
+        const int64_t ab = base(a.space);
+        if (ab < 0) continue;                        // parameters and the borrowed inputs: not in the workspace
+        for (int k = 0; k < K(); ++k)
+            for (const ZeroChunk& c : zero_all) {
+                const int64_t lo = base(SP_GRAD) + shift(SP_GRAD, k) + c.off;
+                if (ab + a.lo < lo + c.len && lo < ab + a.hi) return;
+            }
+    }
+    zero_ride = first;
 }
 
 // two column blocks of one row-major matrix (row pitch ld), given by the offsets of their first elements from the matrix's
@@ -1886,27 +1928,38 @@ static Bases make_bases(const mst_plan* p, const float* params, float* gparams, 
     return b;
 }
 
-static int run_step(const mst_plan* p, const Step& s, const Bases& b, hipStream_t st) {
+// with_zero: the launch also clears the whole-model zero list (the K_GEMM step mst_plan::zero_ride names, in mst_train_iteration)
+static int run_step(const mst_plan* p, const Step& s, const Bases& b, hipStream_t st, bool with_zero = false) {
     if (s.carried) return 0;              // launched by the K_GEMM step of its level
     switch (s.kind) {
     case K_GEMM: case K_GEMM_FOLD: {
         const Riders& q = s.ride;
         const int clips = s.count / s.b, gat_blocks = std::min(512, (q.gat_rows + GATHER_RIDER_ROWS - 1) / GATHER_RIDER_ROWS);
-        const GemmRiders r{p->segreds.dev + q.seg_first, q.seg_members, q.seg_groups, p->gathers.dev + q.gat_first, q.gat_members, gat_blocks};
-        const int e = launch_gemm(p->gemms.dev + s.first, p->d_gemm_owner + s.c, s.b, s.a, clips, p->mfma, b, st, &r);
-        return e ? e : launch_segred2(p->segreds.dev + q.seg_first, q.seg_members * clips, q.seg_stage2, b, st);
+        GemmRiders r{p->segreds.dev + q.seg_first, q.seg_members, q.seg_groups, p->gathers.dev + q.gat_first, q.gat_members, gat_blocks};
+        for (int large = 0; large < 2; ++large) {
+            const CombRide& c = q.comb[large];
+            if (!c.sites) continue;
+            r.comb[large] = {p->combines.dev + c.first, c.sites, large ? (c.nblk + 3) / 4 : 1,
+                             large ? (c.bwd ? COMB_RIDE_REDUCE : COMB_RIDE_SUMSQ) : (c.bwd ? COMB_RIDE_SMALL_B : COMB_RIDE_SMALL_F)};
+        }
+        if (with_zero) { r.zero = p->d_zero_all; r.zero_chunks = (int)p->zero_all.size(); r.zero_stride = p->act_top; }
+        int e = launch_gemm(p->gemms.dev + s.first, p->d_gemm_owner + s.c, s.b, s.a, clips, p->mfma, b, st, &r);
+        if (!e) e = launch_segred2(p->segreds.dev + q.seg_first, q.seg_members * clips, q.seg_stage2, b, st);
+        if (!e && q.comb[1].sites)       // the second phase of a carried large combine: directly behind the carrier
+            e = launch_combine_phase(p->combines.dev + q.comb[1].first, q.comb[1].nblk, q.comb[1].bwd ? 3 : 1, b, st, q.comb[1].sites * clips, 1, 1);
+        return e;
     }
     case K_GATHER: return launch_gather(p->gathers.dev + s.first, s.count, s.a, b, st);
     case K_SEGRED: return launch_segred(p->segreds.dev + s.first, s.count / p->K(), s.a, p->K(), s.b, b, st);
     case K_LSTM_T: return launch_lstm_transpose(p->lstms.dev + s.first, s.count, s.b, p->lstms.sched[s.first].multi, b, st);
     case K_LSTM_F: return launch_lstm_fwd(p->lstms.dev + s.first, s.count, s.a, s.b, p->lstms.sched[s.first].multi, b, st);
     case K_LSTM_B: return launch_lstm_bwd(p->lstms.dev + s.first, s.count, s.a, s.b, p->lstms.sched[s.first].multi, b, st);
-    case K_COMB_F: return launch_combine_fwd(p->combines.dev + s.first, s.count, s.a, s.b == 0 ? (p->d.C <= 4 ? 2 : 1) : 0, b, st);
-    case K_COMB_B: return launch_combine_bwd(p->combines.dev + s.first, s.count, s.a, s.b == 0 ? (p->d.C <= 4 ? 2 : 1) : 0, b, st);
-    case K_COMB_F1: return launch_combine_phase(p->combines.dev + s.first, s.a, 0, b, st);
-    case K_COMB_F2: return launch_combine_phase(p->combines.dev + s.first, s.a, 1, b, st);
-    case K_COMB_B1: return launch_combine_phase(p->combines.dev + s.first, s.a, 2, b, st);
-    case K_COMB_B2: return launch_combine_phase(p->combines.dev + s.first, s.a, 3, b, st);
+    case K_COMB_F: return launch_combine_fwd(p->combines.dev + s.first, s.count, s.a, s.b == 0 ? (p->mc4() ? 2 : 1) : 0, p->mc4(), b, st);
+    case K_COMB_B: return launch_combine_bwd(p->combines.dev + s.first, s.count, s.a, s.b == 0 ? (p->mc4() ? 2 : 1) : 0, p->mc4(), b, st);
+    case K_COMB_F1: return launch_combine_phase(p->combines.dev + s.first, s.a, 0, b, st, 1, p->mc4());
+    case K_COMB_F2: return launch_combine_phase(p->combines.dev + s.first, s.a, 1, b, st, 1, p->mc4());
+    case K_COMB_B1: return launch_combine_phase(p->combines.dev + s.first, s.a, 2, b, st, 1, p->mc4());
+    case K_COMB_B2: return launch_combine_phase(p->combines.dev + s.first, s.a, 3, b, st, 1, p->mc4());
     case K_COPY_F: return launch_copy_rows(p->copies.dev + s.first, p->copies.host[s.first], 0, b, st);
     case K_COPY_B: return launch_copy_rows(p->copies.dev + s.first, p->copies.host[s.first], 1, b, st);
     case K_FOLD: return launch_fold(p->folds.dev + s.first, 0, b, st);
@@ -1935,7 +1988,8 @@ static int run_step(const mst_plan* p, const Step& s, const Bases& b, hipStream_
 }
 
 // Run one pass (a scheduled list filtered by stage) on the caller's stream.
-static int run_pass(const mst_plan* p, const std::vector<Step>& list, int mask, const Bases& b0, hipStream_t main, bool tags_cleared = false) {
+static int run_pass(const mst_plan* p, const std::vector<Step>& list, int mask, const Bases& b0, hipStream_t main, bool tags_cleared = false,
+                    int zero_step = -1 /* index of the step whose launch also clears the zero list */) {
     Bases b = b0;
     if (mask == MST_STAGE_ALL) b.flags |= MST_BF_ALL_STAGES;            // p->list(mask, .) is the whole-model list then
     auto runs = [&](const Step& s) {
@@ -1961,7 +2015,7 @@ static int run_pass(const mst_plan* p, const std::vector<Step>& list, int mask, 
             for (int w = 0; w < 3; ++w)
                 if (s.wait[w] >= 0 && hipStreamWaitEvent(st, ss->ev[s.wait[w]], 0) != hipSuccess) return MST_ERR_LAUNCH;
         }
-        int e = run_step(p, s, b, st);
+        int e = run_step(p, s, b, st, zero_step >= 0 && &s == &list[zero_step]);
         if (e) return e < 0 ? e : MST_ERR_LAUNCH;
         if (ss && s.signal >= 0 && hipEventRecord(ss->ev[s.signal], st) != hipSuccess) return MST_ERR_LAUNCH;
     }
@@ -2034,10 +2088,11 @@ extern "C" int32_t mst_train_iteration(const mst_plan* p, const float* params, f
                                        const float* pitched, const float* unpitched, float* losses, mst_stream stream) {
     if (!p || !params || !gparams || !ws || !pitched) return MST_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    int e = mst_zero_grads(p, MST_STAGE_ALL, ws, stream);
+    // the zero list (with the exchange tags) rides on the first forward launch where the plan proved that launch independent of it
+    int e = p->zero_ride >= 0 ? 0 : mst_zero_grads(p, MST_STAGE_ALL, ws, stream);
     if (e) return e;
     if (p->d.has_unpitched && !unpitched) return MST_ERR_ARG;
-    e = run_pass(p, p->list(MST_STAGE_ALL, 0), MST_STAGE_ALL, make_bases(p, params, nullptr, ws, pitched, unpitched), st, p->tags_in_zero);
+    e = run_pass(p, p->list(MST_STAGE_ALL, 0), MST_STAGE_ALL, make_bases(p, params, nullptr, ws, pitched, unpitched), st, p->tags_in_zero, p->zero_ride);
     if (e) return e;
     const bool U = p->d.has_unpitched != 0;
     const int K = p->K();
@@ -2275,9 +2330,25 @@ extern "C" int64_t mst_plan_zero_floats(const mst_plan* p, int32_t mask) {
 extern "C" int32_t mst_plan_step_carried(const mst_plan* p, int32_t mask, int32_t backward, int32_t* carried) {
     if (!p || !carried) return MST_ERR_ARG;
     int n = 0;
-    for (auto& s : p->list(mask, backward)) if (s.stage & mask) carried[n++] = !s.carried ? 0 : ((s.kind == K_SEGRED && s.b > 0) ? 2 : 1);
+    for (auto& s : p->list(mask, backward))
+        if (s.stage & mask) carried[n++] = (!s.carried || (s.kind != K_GATHER && s.kind != K_SEGRED)) ? 0 : ((s.kind == K_SEGRED && s.b > 0) ? 2 : 1);
     return n;
 }
+
+// every kind: 0 = own launch(es), 1 = the whole step is in its level's GEMM launch, 2 = the first stage is carried and the second
+// stage is a launch behind the carrier
+extern "C" int32_t mst_plan_step_riders(const mst_plan* p, int32_t mask, int32_t backward, int32_t* out) {
+    if (!p || !out) return MST_ERR_ARG;
+    int n = 0;
+    for (auto& s : p->list(mask, backward)) {
+        if (!(s.stage & mask)) continue;
+        const bool two = (s.kind == K_SEGRED && s.b > 0) || ((s.kind == K_COMB_F || s.kind == K_COMB_B) && s.b != 0);
+        out[n++] = !s.carried ? 0 : (two ? 2 : 1);
+    }
+    return n;
+}
+
+extern "C" int32_t mst_plan_zero_rides(const mst_plan* p) { return !p ? MST_ERR_ARG : (p->zero_ride >= 0 ? 1 : 0); }
 
 extern "C" int32_t mst_plan_step_count(const mst_plan* p, int32_t mask, int32_t backward) {
     if (!p) return MST_ERR_ARG;

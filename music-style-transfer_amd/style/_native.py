@@ -125,6 +125,8 @@ _SIGS = {
     'mst_plan_step_count': (C.c_int32, [_P, C.c_int32, C.c_int32]),
     'mst_plan_step_info': (C.c_int32, [_P, C.c_int32, C.c_int32, _P]),
     'mst_plan_step_carried': (C.c_int32, [_P, C.c_int32, C.c_int32, _P]),
+    'mst_plan_step_riders': (C.c_int32, [_P, C.c_int32, C.c_int32, _P]),
+    'mst_plan_zero_rides': (C.c_int32, [_P]),
     'mst_plan_step_gemms': (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32]),
     'mst_plan_time_steps': (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P]),
     'mst_audio_plan_create': (_P, [C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32)]),
@@ -394,6 +396,23 @@ class Plan:
         got = self.lib.mst_plan_step_carried(self.handle, mask, int(backward), out.ctypes.data)
         check(got if got < 0 else 0, 'mst_plan_step_carried')
         return out.tolist()
+
+    def step_riders(self, mask=STAGE_ALL, backward=False):
+        """One int per step of the pass, for every step kind (gathers, segment reduces, combines): 0 = launched on its own,
+        1 = the whole step is in its level's GEMM launch, 2 = its first stage is carried and its second stage is a launch
+        behind the carrier."""
+        import numpy as np
+        n = self.lib.mst_plan_step_count(self.handle, mask, int(backward))
+        out = np.zeros(n, np.int32)
+        got = self.lib.mst_plan_step_riders(self.handle, mask, int(backward), out.ctypes.data)
+        check(got if got < 0 else 0, 'mst_plan_step_riders')
+        return out.tolist()
+
+    def zero_rides(self):
+        """1 if train_iteration clears the gradient zero list inside its first forward launch, 0 if by a launch of its own."""
+        got = self.lib.mst_plan_zero_rides(self.handle)
+        check(got if got < 0 else 0, 'mst_plan_zero_rides')
+        return got
 
     def step_gemms(self, mask, backward, step, cap=2048):
         """[(M, N, K, k_splits, fold_rows, workgroups)] of the members (one clip's worth) of GEMM launch step `step`."""
