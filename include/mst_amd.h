@@ -361,17 +361,30 @@ int32_t mst_plan_step_info(const mst_plan* p, int32_t stage_mask, int32_t backwa
  * its workgroups in front of the GEMM members' (one-stream, merged plans on the 32x32 tiling only); 2 = a carried two-stage segment
  * reduce: its first stage rides, its second stage stays a launch, directly behind the GEMM launch.  mst_plan_launch_count counts
  * a carried step's first stage as 0 launches.  mst_plan_time_steps times the GEMM step together with everything it carries and
- * reports a carried step as a row of 0 ms with its own FLOPs / bytes.  Returns the step count. */
+ * reports a carried step as a row of 0 ms with its own FLOPs / bytes.  Always 0 for LSTM steps, carried or not (and every kind but
+ * gathers and segment reduces): mst_plan_step_carrier reports those.  Returns the step count. */
 int32_t mst_plan_step_carried(const mst_plan* p, int32_t stage_mask, int32_t backward, int32_t* carried);
 /* The same for every step kind a GEMM launch can carry (gathers, segment reduces, and the combine steps of plans with at most 4
  * channels): 0 = own launch(es); 1 = the whole step is in its level's GEMM launch (a gather, a one-stage segment reduce, a small
  * combine site); 2 = the first stage is carried and the second stage is a launch directly behind the carrier (a two-stage segment
- * reduce, a large combine).  mst_plan_step_carried keeps reporting gathers and segment reduces only.  Returns the step count. */
+ * reduce, a large combine).  mst_plan_step_carried keeps reporting gathers and segment reduces only.  Always 0 for LSTM steps,
+ * carried or not: mst_plan_step_carrier reports those.  Returns the step count. */
 int32_t mst_plan_step_riders(const mst_plan* p, int32_t stage_mask, int32_t backward, int32_t* out);
 /* 1 = mst_train_iteration clears the whole-model zero list (mst_zero_grads' ranges, with the LSTM exchange tags) inside its first
  * forward launch: that launch is a GEMM step of a plan that carries riders, and the plan proved that nothing the launch reads or
  * writes overlaps a zero chunk.  0 = the zero list is a launch of its own, as in mst_zero_grads. */
 int32_t mst_plan_zero_rides(const mst_plan* p);
+/* One int per step of the pass: the index, within the same list, of the step whose launch runs it (the GEMM step of its level that
+ * carries it: every carried kind), or -1 for a step with a launch of its own.  Besides gathers, segment reduces and combines
+ * that is a backward LSTM step whose hidden sizes are all <= 8 and that would not take the grouped flavour, on a level with a
+ * GEMM step (of its own stage where stages run separately): one wave of a gemm_kernel rider block runs one sequence.  Forward
+ * LSTM steps and larger hidden sizes keep their launch.  Returns the step count. */
+int32_t mst_plan_step_carrier(const mst_plan* p, int32_t stage_mask, int32_t backward, int32_t* out);
+/* The LSTM launches of a plan whose hidden sizes are all <= 16 (and that do not take the grouped flavour of batched plans) run on
+ * the one-wave kernels: one wave per sequence, no workgroup barrier.  on = 0 makes them use the register-flavour kernels of
+ * H <= 64 instead (bit-identical results; for tests and profiling); on = 1 is the default.  MST_ERR_UNSUPPORTED on a plan in
+ * which a GEMM launch carries an LSTM step (mst_plan_step_carrier): meant for no_merge = 1 plans. */
+int32_t mst_plan_set_lstm_small(mst_plan* p, int32_t on);
 /* (new) instrumentation: the members of GEMM launch step `step` of a pass, one clip's worth, 6 values each:
  * {M, N, K, k-splits, folded rows per clip (0 = not folded), workgroups}.  Returns the member count (<= cap). */
 int32_t mst_plan_step_gemms(const mst_plan* p, int32_t stage_mask, int32_t backward, int32_t step, int32_t* out, int32_t cap);

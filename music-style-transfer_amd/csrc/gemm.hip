@@ -19,6 +19,7 @@
 // (tile, k-split) workgroups; k-splits of weight gradients write deterministic slabs that are
 // reduced later in order.
 #include "combine_body.h"
+#include "lstm_small_body.h"
 
 __device__ __forceinline__ float act_fwd(int act, float z, int col) {
     if (act == ACT_LEAKY) return z > 0.f ? z : z * LEAKY;
@@ -751,14 +752,28 @@ __device__ __forceinline__ void segred_group(const SegRedDesc* __restrict__ desc
 // (workgroup-uniform) variant picks the instantiation.  That lets the scheduler put *independent*
 // GEMMs of different kinds — e.g. the weight-gradient and input-gradient GEMMs of one layer, or
 // all small Linears of one dependency level — into a single launch.
-// The launch also carries its level's combine steps, gathers and stage-1 segment reduces (GemmRiders): a clip's block range starts
-// with the combine blocks (two passes over a site around a reduction: the longest walk, so dispatched first), then the
+// The launch also carries its level's backward LSTM step of hidden sizes <= 8, combine steps, gathers and stage-1 segment reduces
+// (GemmRiders): a clip's block range starts with the LSTM blocks (a whole recurrence per wave: the longest walk of all), then
+// the combine blocks (two passes over a site around a reduction: the longest walk, so dispatched first), then the
 // segment-reduce blocks (four of segred_kernel's 256-lane groups each), then the gather blocks (sixteen rows each, one per wave),
 // then the zero list's chunks (a train iteration's first forward launch; the shortest walk), then the GEMM members' tiles.
 // Segment-reduce, gather and zero blocks touch no LDS and meet no barrier; a combine block's few hundred bytes of LDS overlay
 // smem, and every lane of it reaches every barrier.  No workgroup waits for another one.
 // block `lb` of a clip's rider blocks
 __device__ __forceinline__ void gemm_rider_block(const GemmRiders& r, const int clip, int lb, const Bases& b, float* smem) {
+    // the backward LSTM recurrences first (the longest walk of the launch): wave w of block `blk` of member m runs sequence 16 blk + w in
+    // its own 4 KB slice of smem; no workgroup barrier is reached by any wave of such a block
+    const int lstm_blocks = r.lstm_members * r.lstm_blocks;
+    if (lb < lstm_blocks) {
+        const int m = lb / r.lstm_blocks, wave = MST_UNIFORM(threadIdx.x >> 6), bi = (lb - m * r.lstm_blocks) * (GEMM_THREADS / 64) + wave;
+        const LstmDesc d = r.lstms[clip * r.lstm_members + m];
+        if (bi >= d.B) return;
+        float* slice = smem + wave * LSTM_SW_LDS;
+        const int lane = threadIdx.x & 63;
+        lstm_small_bwd_body<LSTM_RIDE_H, true>(d, bi, lane, b, slice);
+        return;
+    }
+    lb -= lstm_blocks;
     const int seg_blocks = (r.seg_groups + 3) >> 2, gat_blocks = r.gat_members * r.gat_blocks;
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
@@ -795,7 +810,7 @@ __device__ __forceinline__ void gemm_rider_block(const GemmRiders& r, const int 
 __global__ __launch_bounds__(GEMM_THREADS) void gemm_kernel(const GemmDesc* __restrict__ descs, const int* __restrict__ owner, int count, int blocks_per_clip, int rider_blocks, Bases b, GemmRiders r) {
     // A tile | B tile; the final reduce overlays the whole block with one 32x32 partial tile per wave
     constexpr int TILE_F = GEMM_BK * (GEMM_BM + GEMM_PAD), RED_F = (GEMM_THREADS / 64) * GEMM_BM * GEMM_BN;
-    __shared__ float smem[(2 * TILE_F > RED_F) ? 2 * TILE_F : RED_F];
+    __shared__ __attribute__((aligned(16))) float smem[(2 * TILE_F > RED_F) ? 2 * TILE_F : RED_F];
     float (*As)[GEMM_BM + GEMM_PAD] = reinterpret_cast<float (*)[GEMM_BM + GEMM_PAD]>(smem);
     float (*Bs)[GEMM_BN + GEMM_PAD] = reinterpret_cast<float (*)[GEMM_BN + GEMM_PAD]>(smem + TILE_F);
     // flat 1-D grid: clip-major; inside a clip's block range, behind the riders, member y owns [blk_begin, blk_begin + tiles * ksplit)
@@ -844,7 +859,7 @@ int gemm_variant(const GemmDesc& g) {
     return -1;
 }
 
-int gemm_rider_blocks(const GemmRiders& r) { return r.comb[0].sites * r.comb[0].blocks + r.comb[1].sites * r.comb[1].blocks + (r.seg_groups + 3) / 4 + r.gat_members * r.gat_blocks + r.zero_chunks; }
+int gemm_rider_blocks(const GemmRiders& r) { return r.lstm_members * r.lstm_blocks + r.comb[0].sites * r.comb[0].blocks + r.comb[1].sites * r.comb[1].blocks + (r.seg_groups + 3) / 4 + r.gat_members * r.gat_blocks + r.zero_chunks; }
 
 int launch_gemm(const GemmDesc* dev_descs, const int* dev_owner, int members, int blocks_per_clip, int clips, int mfma, Bases b, hipStream_t s, const GemmRiders* riders) {
     if (members <= 0 || blocks_per_clip <= 0 || clips <= 0) return 0;

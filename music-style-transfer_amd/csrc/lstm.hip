@@ -11,19 +11,15 @@
 // is LDS-only (MST_LDS_BARRIER), so streamed stores / prefetches never stall a step.  H > 256 (wide bar / style widths, up to
 // 1024): the same over 1024 lanes with several gate rows per lane.  A launch never mixes the three bands (lstm_band).
 #include "mst_common.h"
+#include "lstm_small_body.h"
 
 #define LSTM_ZS 8192        // floats of LDS holding staged per-step operands in the register flavours
 #define LSTM_MCH 32         // steps whose streamed operands the multi-workgroup backward stages in LDS at once
-__device__ __forceinline__ float sigm(float x) { return MST_FAST_RCP(1.f + MST_FAST_EXP(-x)); }
-__device__ __forceinline__ float tanh_fast(float x) { return 2.f * sigm(2.f * x) - 1.f; }
 __device__ __forceinline__ float wsum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
-
-typedef float lstm_f4 __attribute__((ext_vector_type(4)));
-typedef float lstm_f4u __attribute__((ext_vector_type(4), aligned(4)));       // a 16-byte load from a 4-byte aligned address
 
 // REG (H <= 64) launches at most 256 lanes, so it may use the whole register file of one wave per SIMD
 template <bool REG>
@@ -348,6 +344,22 @@ __global__ __launch_bounds__(REG ? 256 : 1024) void lstm_bwd_kernel(const LstmDe
         MST_LDS_BARRIER();
     }
 #undef LSTM_LOAD
+}
+
+// ---- one-wave flavour (H <= LSTM_SH): the bodies are in lstm_small_body.h -------------------------
+template <int KP>
+__global__ __launch_bounds__(64) void lstm_fwd_small_kernel(const LstmDesc* __restrict__ descs, Bases b) {
+    const LstmDesc d = descs[blockIdx.y];
+    if ((int)blockIdx.x >= d.B) return;
+    __shared__ __attribute__((aligned(16))) float lds[LSTM_SW_LDS];
+    lstm_small_fwd_body<KP>(d, blockIdx.x, threadIdx.x, b, lds);
+}
+template <int KP>
+__global__ __launch_bounds__(64) void lstm_bwd_small_kernel(const LstmDesc* __restrict__ descs, Bases b) {
+    const LstmDesc d = descs[blockIdx.y];
+    if ((int)blockIdx.x >= d.B) return;
+    __shared__ __attribute__((aligned(16))) float lds[LSTM_SW_LDS];
+    lstm_small_bwd_body<KP>(d, blockIdx.x, threadIdx.x, b, lds);
 }
 
 // ---- wide flavour (LSTM_L2H < H <= LSTM_WH) -------------------------------------------------------
@@ -824,12 +836,7 @@ __global__ __launch_bounds__(256) void lstm_multi_fwd_kernel(const LstmDesc* __r
 // a * b + c as the device build of lstm_multi_bwd_kernel has always evaluated its three of them: ONE fma (hipcc contracts by
 // default).  Written out because which products get contracted otherwise depends on what the compiler vectorises around
 // them: with the operands coming from LDS it packed the multiplications in pairs first and the results moved by an ulp.  The
-// interpreter's x86-64 build does not contract and keeps its two roundings.
-#ifdef HIPSIM
-#define LSTM_MULADD(a, b, c) ((a) * (b) + (c))
-#else
-#define LSTM_MULADD(a, b, c) __builtin_fmaf((a), (b), (c))
-#endif
+// interpreter's x86-64 build does not contract and keeps its two roundings.  (LSTM_MULADD, defined with the one-wave flavour.)
 
 // The G / 256 = 3 granules a lane of the backward kernel owns (256 apart), waited for JOINTLY: a poll round issues all the
 // loads, waits once and latches the values whose tag matches; only the rest are polled again, one s_sleep per round.  Three
@@ -1037,13 +1044,25 @@ static bool lstm_grouped(int, int maxB) { return maxB >= 2 * LSTM_NS; }      // 
 static bool lstm_grouped(int count, int maxB) { return maxB >= 2 * LSTM_NS && (int64_t)count * maxB >= 2048; }
 #endif
 
-int launch_lstm_fwd(const LstmDesc* dev_descs, int count, int maxB, int maxH, int multi, Bases b, hipStream_t s) {
+// one wave per sequence where the whole recurrence fits one (and the launch does not take the grouped flavour)
+bool lstm_small(int count, int maxB, int maxH) { return maxH <= LSTM_SH && !lstm_grouped(count, maxB); }
+#define LSTM_SMALL_LAUNCH(K)                                                                                         \
+    switch ((maxH + 3) / 4) {                                                                                        \
+    case 1: hipLaunchKernelGGL((K<4>), dim3(maxB, count), dim3(64), 0, s, dev_descs, b); break;                      \
+    case 2: hipLaunchKernelGGL((K<8>), dim3(maxB, count), dim3(64), 0, s, dev_descs, b); break;                      \
+    case 3: hipLaunchKernelGGL((K<12>), dim3(maxB, count), dim3(64), 0, s, dev_descs, b); break;                     \
+    default: hipLaunchKernelGGL((K<16>), dim3(maxB, count), dim3(64), 0, s, dev_descs, b); break;                    \
+    }
+
+int launch_lstm_fwd(const LstmDesc* dev_descs, int count, int maxB, int maxH, int multi, int small, Bases b, hipStream_t s) {
     if (count <= 0) return 0;
     if (multi) {
         MST_LAUNCH_CORESIDENT(lstm_multi_fwd_kernel, dim3(LSTM_NB, count), dim3(256), s, dev_descs, b);
         return (int)hipGetLastError();
     }
-    if (maxH <= 64 && lstm_grouped(count, maxB))
+    if (small && lstm_small(count, maxB, maxH)) {
+        LSTM_SMALL_LAUNCH(lstm_fwd_small_kernel)
+    } else if (maxH <= 64 && lstm_grouped(count, maxB))
         hipLaunchKernelGGL(lstm_fwd_group_kernel, dim3((maxB + LSTM_NS - 1) / LSTM_NS, count), dim3(256), 0, s, dev_descs, b);
     else if (maxH <= 64)
         hipLaunchKernelGGL((lstm_fwd_kernel<true>), dim3(maxB, count), dim3(block_for(maxH)), 0, s, dev_descs, b);
@@ -1054,13 +1073,15 @@ int launch_lstm_fwd(const LstmDesc* dev_descs, int count, int maxB, int maxH, in
     return (int)hipGetLastError();
 }
 
-int launch_lstm_bwd(const LstmDesc* dev_descs, int count, int maxB, int maxH, int multi, Bases b, hipStream_t s) {
+int launch_lstm_bwd(const LstmDesc* dev_descs, int count, int maxB, int maxH, int multi, int small, Bases b, hipStream_t s) {
     if (count <= 0) return 0;
     if (multi) {
         MST_LAUNCH_CORESIDENT(lstm_multi_bwd_kernel, dim3(LSTM_NB, count), dim3(256), s, dev_descs, b);
         return (int)hipGetLastError();
     }
-    if (maxH <= 64 && lstm_grouped(count, maxB))
+    if (small && lstm_small(count, maxB, maxH)) {
+        LSTM_SMALL_LAUNCH(lstm_bwd_small_kernel)
+    } else if (maxH <= 64 && lstm_grouped(count, maxB))
         hipLaunchKernelGGL(lstm_bwd_group_kernel, dim3((maxB + LSTM_NS - 1) / LSTM_NS, count), dim3(256), 0, s, dev_descs, b);
     else if (maxH <= 64)
         hipLaunchKernelGGL((lstm_bwd_kernel<true>), dim3(maxB, count), dim3(block_for(maxH)), 0, s, dev_descs, b);

@@ -176,7 +176,13 @@ struct GemmRiders {
     // (a level has at most one step of small and one of large sites per pass: two slots)
     struct Comb { const CombineDesc* descs; int32_t sites, blocks, kind; } comb[2];     // sites per clip, workgroups per site, COMB_RIDE_*
     const ZeroChunk* zero; int32_t zero_chunks; int64_t zero_stride;          // chunks per clip (one workgroup each), floats between two clips' gradient slices
+    // the level's backward LSTM step of hidden sizes <= LSTM_RIDE_H (one-wave body, W_hh in the wave's LDS slice): members per
+    // clip, workgroups per member (sixteen sequences each, one per wave)
+    const struct LstmDesc* lstms; int32_t lstm_members, lstm_blocks;
 };
+// largest H a gemm_kernel launch carries, backward recurrences only: with the KP = 8 backward body gemm_kernel keeps its 87 VGPRs
+// (with the forward body beside it: 89; with KP = 12: 126); at H = 16 W_hh alone fills a wave's 4 KB slice
+#define LSTM_RIDE_H 8
 
 // ---- LSTM recurrence
 struct LstmDesc {
@@ -376,8 +382,10 @@ int gemm_blocks(const GemmDesc& g, int mfma);       // workgroups of one member 
 int launch_segred(const SegRedDesc* dev_descs, int members, int blocks_per_clip, int clips, int stage2_blocks, Bases b, hipStream_t s);
 int launch_segred2(const SegRedDesc* dev_descs, int count, int stage2_blocks, Bases b, hipStream_t s);      // stage 2 alone (stage 1 rode on a GEMM launch)
 int launch_lstm_transpose(const LstmDesc* dev_descs, int count, int maxH, int multi, Bases b, hipStream_t s);
-int launch_lstm_fwd(const LstmDesc* dev_descs, int count, int maxB, int maxH, int multi, Bases b, hipStream_t s);
-int launch_lstm_bwd(const LstmDesc* dev_descs, int count, int maxB, int maxH, int multi, Bases b, hipStream_t s);
+// small: launches the one-wave flavour may take (lstm_small) do; 0 keeps them on the register flavour (mst_plan_set_lstm_small)
+int launch_lstm_fwd(const LstmDesc* dev_descs, int count, int maxB, int maxH, int multi, int small, Bases b, hipStream_t s);
+int launch_lstm_bwd(const LstmDesc* dev_descs, int count, int maxB, int maxH, int multi, int small, Bases b, hipStream_t s);
+bool lstm_small(int count, int maxB, int maxH);      // the launch takes the one-wave flavour: H <= 16 and not the grouped one
 int lstm_multi_blocks_per_cu();      // workgroups of the multi-workgroup LSTM kernels one CU holds at once (occupancy API)
 int launch_combine_fwd(const CombineDesc* dev_descs, int count, int max_nblk, int all_small, int mc4, Bases b, hipStream_t s);
 int launch_combine_bwd(const CombineDesc* dev_descs, int count, int max_nblk, int all_small, int mc4, Bases b, hipStream_t s);

@@ -251,12 +251,14 @@ template <class D> struct DescTable {
 // and K_COMB_F / K_COMB_B steps (slot 0: small sites, slot 1: large sites, whose second phase is a launch behind the carrier;
 // first descriptor, sites per clip, most workgroups of a site, the pass)
 struct CombRide { int first = 0, sites = 0, nblk = 0, bwd = 0; };
-struct Riders { int seg_first = 0, seg_members = 0, seg_groups = 0, seg_stage2 = 0, gat_first = 0, gat_members = 0, gat_rows = 0; CombRide comb[2]; };
+struct Riders { int seg_first = 0, seg_members = 0, seg_groups = 0, seg_stage2 = 0, gat_first = 0, gat_members = 0, gat_rows = 0; CombRide comb[2];
+                // ... and K_LSTM_B step of hidden sizes <= LSTM_RIDE_H: first descriptor, members per clip, most sequences of a member
+                int lstm_first = 0, lstm_members = 0, lstm_maxB = 0; };
 struct Step { int kind, first, count, a, b, stage; int c = 0; int lvl = 0; int chain = -1; int signal = -1; int wait[3] = {-1, -1, -1};
               int carried = 0; Riders ride; };
 // c: GEMM steps — offset of the step's block -> member table; lvl: dependency level in its scheduled pass; chain / signal / wait: the stream the
 // launch goes to, the event slot recorded behind it and the slots its stream waits for in front of it (assign_streams; chain -1 = caller's stream)
-// carried: a gather / segment-reduce / combine step that stays in the list (dependencies, first-writer flags, instrumentation) but is launched by
+// carried: a gather / segment-reduce / combine / small backward LSTM step that stays in the list (dependencies, first-writer flags, instrumentation) but is launched by
 // the K_GEMM step of its level, whose `ride` names its descriptors
 struct Acc { int space; int64_t lo, hi; bool w; bool accum = false, dense = true; };   // accum: a += writer; dense: covers [lo, hi) fully
 struct Op { int stage; std::vector<Step> fwd, bwd; };
@@ -291,6 +293,7 @@ struct mst_plan {
     int err = 0;
     mst_plan_options opt{};       // as given to mst_plan_create_ex (zeros = defaults)
     int mfma = 0;                 // GEMM tiling of this plan: 1 = 64x64 tiles (batched, FLOP-bound plans), 0 = 32x32 split-K tiles (latency)
+    int lstm_small_on = 1;        // H <= 16 LSTM launches take the one-wave kernels (mst_plan_set_lstm_small; 0: the register flavour)
 
     // bar tiling (mst_plan_options.tile_rows > 0): this rank owns bars [tile_r0, tile_r0 + tile_rows) of the d.R bars
     bool tiled() const { return opt.tile_rows > 0; }
@@ -1529,7 +1532,11 @@ void mst_plan::schedule_pass(const std::vector<Step>& seq, std::vector<Step>& ou
         if (!mixes()) continue;
         for (size_t e = lv_begin; e < out.size(); ++e) {
             const bool comb = (out[e].kind == K_COMB_F || out[e].kind == K_COMB_B) && mc4();
-            if (out[e].kind != K_GATHER && out[e].kind != K_SEGRED && !comb) continue;
+            // a backward LSTM step whose launch would take the one-wave kernel (not the grouped flavour) and whose W_hh fits the rider's
+            // LDS slice beside the staged operands (the forward body beside it costs gemm_kernel two VGPRs: it keeps its launch)
+            const bool lstm = out[e].kind == K_LSTM_B && out[e].b <= LSTM_RIDE_H &&
+                              lstm_small(out[e].count, out[e].a, out[e].b);
+            if (out[e].kind != K_GATHER && out[e].kind != K_SEGRED && !comb && !lstm) continue;
             for (size_t c = lv_begin; c < out.size(); ++c) {
                 Step& g = out[c];
                 if (g.kind != K_GEMM || (!across_stages && g.stage != out[e].stage)) continue;
@@ -1537,6 +1544,7 @@ void mst_plan::schedule_pass(const std::vector<Step>& seq, std::vector<Step>& ou
                 if (s.kind == K_GATHER && !g.ride.gat_members) { g.ride.gat_first = s.first; g.ride.gat_members = s.count / K(); g.ride.gat_rows = s.a; }
                 else if (s.kind == K_SEGRED && !g.ride.seg_members) { g.ride.seg_first = s.first; g.ride.seg_members = s.count / K(); g.ride.seg_groups = s.a; g.ride.seg_stage2 = s.b; }
                 else if (comb && !g.ride.comb[s.b != 0].sites) g.ride.comb[s.b != 0] = CombRide{s.first, s.count / K(), s.a, s.kind == K_COMB_B};
+                else if (lstm && !g.ride.lstm_members) { g.ride.lstm_first = s.first; g.ride.lstm_members = s.count / K(); g.ride.lstm_maxB = s.a; }
                 else continue;
                 out[e].carried = 1;
                 break;
@@ -1942,6 +1950,8 @@ static int run_step(const mst_plan* p, const Step& s, const Bases& b, hipStream_
             r.comb[large] = {p->combines.dev + c.first, c.sites, large ? (c.nblk + 3) / 4 : 1,
                              large ? (c.bwd ? COMB_RIDE_REDUCE : COMB_RIDE_SUMSQ) : (c.bwd ? COMB_RIDE_SMALL_B : COMB_RIDE_SMALL_F)};
         }
+        if (q.lstm_members) { r.lstms = p->lstms.dev + q.lstm_first; r.lstm_members = q.lstm_members; r.lstm_blocks = (q.lstm_maxB + GEMM_THREADS / 64 - 1) / (GEMM_THREADS / 64);
+}
         if (with_zero) { r.zero = p->d_zero_all; r.zero_chunks = (int)p->zero_all.size(); r.zero_stride = p->act_top; }
         int e = launch_gemm(p->gemms.dev + s.first, p->d_gemm_owner + s.c, s.b, s.a, clips, p->mfma, b, st, &r);
         if (!e) e = launch_segred2(p->segreds.dev + q.seg_first, q.seg_members * clips, q.seg_stage2, b, st);
@@ -1952,8 +1962,8 @@ static int run_step(const mst_plan* p, const Step& s, const Bases& b, hipStream_
     case K_GATHER: return launch_gather(p->gathers.dev + s.first, s.count, s.a, b, st);
     case K_SEGRED: return launch_segred(p->segreds.dev + s.first, s.count / p->K(), s.a, p->K(), s.b, b, st);
     case K_LSTM_T: return launch_lstm_transpose(p->lstms.dev + s.first, s.count, s.b, p->lstms.sched[s.first].multi, b, st);
-    case K_LSTM_F: return launch_lstm_fwd(p->lstms.dev + s.first, s.count, s.a, s.b, p->lstms.sched[s.first].multi, b, st);
-    case K_LSTM_B: return launch_lstm_bwd(p->lstms.dev + s.first, s.count, s.a, s.b, p->lstms.sched[s.first].multi, b, st);
+    case K_LSTM_F: return launch_lstm_fwd(p->lstms.dev + s.first, s.count, s.a, s.b, p->lstms.sched[s.first].multi, p->lstm_small_on, b, st);
+    case K_LSTM_B: return launch_lstm_bwd(p->lstms.dev + s.first, s.count, s.a, s.b, p->lstms.sched[s.first].multi, p->lstm_small_on, b, st);
     case K_COMB_F: return launch_combine_fwd(p->combines.dev + s.first, s.count, s.a, s.b == 0 ? (p->mc4() ? 2 : 1) : 0, p->mc4(), b, st);
     case K_COMB_B: return launch_combine_bwd(p->combines.dev + s.first, s.count, s.a, s.b == 0 ? (p->mc4() ? 2 : 1) : 0, p->mc4(), b, st);
     case K_COMB_F1: return launch_combine_phase(p->combines.dev + s.first, s.a, 0, b, st, 1, p->mc4());
@@ -2343,9 +2353,48 @@ extern "C" int32_t mst_plan_step_riders(const mst_plan* p, int32_t mask, int32_t
     for (auto& s : p->list(mask, backward)) {
         if (!(s.stage & mask)) continue;
         const bool two = (s.kind == K_SEGRED && s.b > 0) || ((s.kind == K_COMB_F || s.kind == K_COMB_B) && s.b != 0);
-        out[n++] = !s.carried ? 0 : (two ? 2 : 1);
+        out[n++] = (!s.carried || s.kind == K_LSTM_F || s.kind == K_LSTM_B) ? 0 : (two ? 2 : 1);      // LSTM steps: mst_plan_step_carrier
     }
     return n;
+}
+
+// for every step of the list: the index, within the same (mask-filtered) list, of the step whose launch runs it; -1 = its own launch
+extern "C" int32_t mst_plan_step_carrier(const mst_plan* p, int32_t mask, int32_t backward, int32_t* out) {
+    if (!p || !out) return MST_ERR_ARG;
+    const std::vector<Step>& L = p->list(mask, backward);
+    std::vector<int> pos(L.size(), -1);             // list index -> index among the steps of `mask`
+    int n = 0;
+    for (size_t i = 0; i < L.size(); ++i) if (L[i].stage & mask) pos[i] = n++;
+    for (size_t i = 0; i < L.size(); ++i) {
+        const Step& s = L[i];
+        if (pos[i] < 0) continue;
+        int at = -1;
+        if (s.carried)
+            for (size_t c = 0; c < L.size() && at < 0; ++c) {
+                const Step& g = L[c];
+                if (g.kind != K_GEMM || g.lvl != s.lvl) continue;
+                const Riders& q = g.ride;
+                const bool mine = (s.kind == K_GATHER && q.gat_members && q.gat_first == s.first) ||
+                                  (s.kind == K_SEGRED && q.seg_members && q.seg_first == s.first) ||
+                                  ((s.kind == K_COMB_F || s.kind == K_COMB_B) && q.comb[s.b != 0].sites && q.comb[s.b != 0].first == s.first &&
+                                   q.comb[s.b != 0].bwd == (s.kind == K_COMB_B)) ||
+                                  (s.kind == K_LSTM_B && q.lstm_members && q.lstm_first == s.first);
+                if (mine) at = pos[c];
+            }
+        out[pos[i]] = at;
+    }
+    return n;
+}
+
+// on = 0: the plan's own-launch H <= 16 LSTM steps use the register-flavour kernels instead of the one-wave ones (tests, profiling)
+extern "C" int32_t mst_plan_set_lstm_small(mst_plan* p, int32_t on) {
+    if (!p) return MST_ERR_ARG;
+    for (int pass = 0; pass < 2; ++pass)
+        for (const std::vector<Step>* L : {&p->sched[pass], &p->sched_all[pass]})
+            for (const Step& s : *L)
+                if ((s.kind == K_LSTM_F || s.kind == K_LSTM_B) && s.carried) return MST_ERR_UNSUPPORTED;      // run inside a gemm_kernel launch
+    p->lstm_small_on = on ? 1 : 0;          // read by run_step at each launch
+    return MST_OK;
 }
 
 extern "C" int32_t mst_plan_zero_rides(const mst_plan* p) { return !p ? MST_ERR_ARG : (p->zero_ride >= 0 ? 1 : 0); }

@@ -127,6 +127,8 @@ _SIGS = {
     'mst_plan_step_carried': (C.c_int32, [_P, C.c_int32, C.c_int32, _P]),
     'mst_plan_step_riders': (C.c_int32, [_P, C.c_int32, C.c_int32, _P]),
     'mst_plan_zero_rides': (C.c_int32, [_P]),
+    'mst_plan_step_carrier': (C.c_int32, [_P, C.c_int32, C.c_int32, _P]),
+    'mst_plan_set_lstm_small': (C.c_int32, [_P, C.c_int32]),
     'mst_plan_step_gemms': (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32]),
     'mst_plan_time_steps': (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P]),
     'mst_audio_plan_create': (_P, [C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32)]),
@@ -407,6 +409,19 @@ class Plan:
         got = self.lib.mst_plan_step_riders(self.handle, mask, int(backward), out.ctypes.data)
         check(got if got < 0 else 0, 'mst_plan_step_riders')
         return out.tolist()
+
+    def step_carrier(self, mask=STAGE_ALL, backward=False):
+        """One int per step of the pass: the index (in the same list) of the step whose launch runs it, -1 = its own launch."""
+        import numpy as np
+        n = self.lib.mst_plan_step_count(self.handle, mask, int(backward))
+        out = np.zeros(n, np.int32)
+        got = self.lib.mst_plan_step_carrier(self.handle, mask, int(backward), out.ctypes.data)
+        check(got if got < 0 else 0, 'mst_plan_step_carrier')
+        return out.tolist()
+
+    def set_lstm_small(self, on):
+        """on = 0: the H <= 16 LSTM launches use the register-flavour kernels instead of the one-wave ones (tests, profiling)."""
+        check(self.lib.mst_plan_set_lstm_small(self.handle, int(on)), 'mst_plan_set_lstm_small')
 
     def zero_rides(self):
         """1 if train_iteration clears the gradient zero list inside its first forward launch, 0 if by a launch of its own."""
