@@ -246,20 +246,19 @@ template <class D> struct DescTable {
     void release() { hipFree(dev); dev = nullptr; }
 };
 
-// What a K_GEMM launch carries besides its members (mst_plan::mixes): its level's K_SEGRED step (first scheduled descriptor, members and
-// 256-lane groups per clip, stage-2 blocks) and K_GATHER step (first descriptor, members per clip, most rows of a member)
-// and K_COMB_F / K_COMB_B steps (slot 0: small sites, slot 1: large sites, whose second phase is a launch behind the carrier;
-// first descriptor, sites per clip, most workgroups of a site, the pass)
-struct CombRide { int first = 0, sites = 0, nblk = 0, bwd = 0; };
-struct Riders { int seg_first = 0, seg_members = 0, seg_groups = 0, seg_stage2 = 0, gat_first = 0, gat_members = 0, gat_rows = 0; CombRide comb[2];
-                // ... and K_LSTM_B step of hidden sizes <= LSTM_RIDE_H: first descriptor, members per clip, most sequences of a member
-                int lstm_first = 0, lstm_members = 0, lstm_maxB = 0; };
+// What a K_GEMM launch can carry besides its members (mst_plan::mixes), one step of its level per slot, in the order of their
+// blocks in the launch: the K_LSTM_B step of hidden sizes <= LSTM_RIDE_H, the K_COMB_F / K_COMB_B step of small sites, the one of
+// large sites (whose second phase is a launch behind the carrier), the K_SEGRED step (its first stage) and the K_GATHER step
+enum { RIDE_LSTM, RIDE_COMB_SMALL, RIDE_COMB_LARGE, RIDE_SEGRED, RIDE_GATHER, RIDE_SLOTS };
 struct Step { int kind, first, count, a, b, stage; int c = 0; int lvl = 0; int chain = -1; int signal = -1; int wait[3] = {-1, -1, -1};
-              int carried = 0; Riders ride; };
+              int carrier = -1; int rider[RIDE_SLOTS] = {-1, -1, -1, -1, -1}; };
 // c: GEMM steps — offset of the step's block -> member table; lvl: dependency level in its scheduled pass; chain / signal / wait: the stream the
 // launch goes to, the event slot recorded behind it and the slots its stream waits for in front of it (assign_streams; chain -1 = caller's stream)
-// carried: a gather / segment-reduce / combine / small backward LSTM step that stays in the list (dependencies, first-writer flags, instrumentation) but is launched by
-// the K_GEMM step of its level, whose `ride` names its descriptors
+// carrier: index, in its scheduled list, of the K_GEMM step whose launch runs this step (-1: its own launch).  A carried step stays in the
+// list (dependencies, first-writer flags, instrumentation); its carrier's rider[slot] is its index, and run_step reads its descriptors
+// (first, count / clips, a, b) from the carried step itself.  Indices, not pointers: the lists are vectors of values
+// a second stage that stays a launch of its own, directly behind the launch that ran the first: a two-stage segment reduce, a combine of large sites
+static bool second_stage(const Step& s) { return (s.kind == K_SEGRED && s.b > 0) || ((s.kind == K_COMB_F || s.kind == K_COMB_B) && s.b != 0); }
 struct Acc { int space; int64_t lo, hi; bool w; bool accum = false, dense = true; };   // accum: a += writer; dense: covers [lo, hi) fully
 struct Op { int stage; std::vector<Step> fwd, bwd; };
 
@@ -288,6 +287,16 @@ struct mst_plan {
     std::vector<SlabBlock> slab_blocks_all; SlabBlock* d_slab_blocks_all = nullptr;
     bool slabs_all_ok = false;
     T t_losses, t_saved, t_gl; int64_t loss_scratch = 0;
+    // clip 0's workspace offsets of what the loss kernels read and write (the gradient of a prediction: the same offset of SP_GRAD)
+    // and the cells of a clip's note tensors; resolved once, where `named` is final.  up: only with an unpitched part
+    struct LossOps { int64_t pp, up, il, mlg, bp, it, mt, bt, losses, saved, gl, np, nu; } loss{};
+    void resolve_loss() {
+        auto at = [&](const char* n) { return named.at(n).off; };
+        const bool U = d.has_unpitched != 0;
+        loss = {at("pitched_pred"), U ? at("unpitched_pred") : 0, at("instruments_pred"), at("mode_pred"), at("bpm_pred"),
+                at("used_instruments"), at("mode"), at("bpm_target"), t_losses.off, t_saved.off, t_gl.off,
+                (int64_t)P() * NF * NPN, U ? (int64_t)Q() * NF * NUN : 0};
+    }
     std::vector<ZeroChunk> zero_stage[3], zero_all;      // gradient ranges mst_zero_grads clears (clip 0 coordinates)
     ZeroChunk* d_zero_stage[3] = {nullptr, nullptr, nullptr}; ZeroChunk* d_zero_all = nullptr;
     int err = 0;
@@ -365,6 +374,12 @@ struct mst_plan {
     }
     int64_t ext0_stride() const { return (int64_t)P() * NF * NPN * NPF; }
     int64_t ext1_stride() const { return (int64_t)Q() * NF * NUN * NUF; }
+    // float offset of an arena from the start of the workspace: every clip's activations, then their gradients, then the scratch
+    // (-1: parameters and the borrowed inputs are not in the workspace)
+    int64_t arena(int space) const {
+        return space == SP_WS ? 0 : space == SP_GRAD ? (int64_t)K() * act_top : space == SP_TMP ? 2 * (int64_t)K() * act_top : -1;
+    }
+    LossBatch loss_batch() const { return {K(), act_top, act_top, tmp_top, ext0_stride(), ext1_stride()}; }      // the clips' strides
     // offset of clip k's slice of `space` relative to clip 0's
     int64_t shift(int space, int k) const {
         switch (space) {
@@ -916,6 +931,7 @@ struct mst_plan {
     void accesses(const Step& s, std::vector<Acc>& out, bool scheduled = false) const;
     void first_writers(std::vector<Step>& list, size_t begin, bool per_stage, std::vector<Acc>& zero);
     void schedule_pass(const std::vector<Step>& seq, std::vector<Step>& out, bool across_stages);
+    int ride_slot(const Step& s) const;
     bool assign_streams(std::vector<Step>& L);
     int n_signals = 0;                 // event slots assign_streams handed out (<= N_EVENTS)
     void schedule();
@@ -1525,31 +1541,35 @@ void mst_plan::schedule_pass(const std::vector<Step>& seq, std::vector<Step>& ou
             }
             out.push_back(m);
         }
-        // Steps of one level are independent, so the level's gather and segment-reduce launches (stage 1) ride on its GEMM launch
-        // (of the same stage where stages may run separately).  The carried steps stay in the list; run_step skips them.
-        // So do its combine steps where no site has more than 4 channels (the flavour whose registers fit gemm_kernel): a small
-        // site's whole step, a large site's first phase.
+        // Steps of one level are independent, so the steps of the level that may ride (ride_slot) go to its GEMM launch (of the same
+        // stage where stages may run separately): each to the first K_GEMM step whose slot is free.  The carried steps stay in the
+        // list; run_step skips them.  `out` was empty when this pass began, so an index into it is the index into the finished list
         if (!mixes()) continue;
         for (size_t e = lv_begin; e < out.size(); ++e) {
-            const bool comb = (out[e].kind == K_COMB_F || out[e].kind == K_COMB_B) && mc4();
-            // a backward LSTM step whose launch would take the one-wave kernel (not the grouped flavour) and whose W_hh fits the rider's
-            // LDS slice beside the staged operands (the forward body beside it costs gemm_kernel two VGPRs: it keeps its launch)
-            const bool lstm = out[e].kind == K_LSTM_B && out[e].b <= LSTM_RIDE_H &&
-                              lstm_small(out[e].count, out[e].a, out[e].b);
-            if (out[e].kind != K_GATHER && out[e].kind != K_SEGRED && !comb && !lstm) continue;
+            const int slot = ride_slot(out[e]);
+            if (slot < 0) continue;
             for (size_t c = lv_begin; c < out.size(); ++c) {
                 Step& g = out[c];
-                if (g.kind != K_GEMM || (!across_stages && g.stage != out[e].stage)) continue;
-                const Step& s = out[e];
-                if (s.kind == K_GATHER && !g.ride.gat_members) { g.ride.gat_first = s.first; g.ride.gat_members = s.count / K(); g.ride.gat_rows = s.a; }
-                else if (s.kind == K_SEGRED && !g.ride.seg_members) { g.ride.seg_first = s.first; g.ride.seg_members = s.count / K(); g.ride.seg_groups = s.a; g.ride.seg_stage2 = s.b; }
-                else if (comb && !g.ride.comb[s.b != 0].sites) g.ride.comb[s.b != 0] = CombRide{s.first, s.count / K(), s.a, s.kind == K_COMB_B};
-                else if (lstm && !g.ride.lstm_members) { g.ride.lstm_first = s.first; g.ride.lstm_members = s.count / K(); g.ride.lstm_maxB = s.a; }
-                else continue;
-                out[e].carried = 1;
+                if (g.kind != K_GEMM || (!across_stages && g.stage != out[e].stage) || g.rider[slot] >= 0) continue;
+                g.rider[slot] = (int)e; out[e].carrier = (int)c;
                 break;
             }
         }
+    }
+}
+
+// The slot in which a scheduled step may ride a K_GEMM launch of its level (-1: it keeps its own launch)
+int mst_plan::ride_slot(const Step& s) const {
+    switch (s.kind) {
+    case K_GATHER: return RIDE_GATHER;
+    case K_SEGRED: return RIDE_SEGRED;            // stage 1; a second stage follows the carrier
+    // combine steps where no site has more than 4 channels (the flavour whose registers fit gemm_kernel): a small site's whole
+    // step, a large site's first phase
+    case K_COMB_F: case K_COMB_B: return !mc4() ? -1 : (s.b != 0 ? RIDE_COMB_LARGE : RIDE_COMB_SMALL);
+    // a backward LSTM step whose launch would take the one-wave kernel (not the grouped flavour) and whose W_hh fits the rider's
+    // LDS slice beside the staged operands (the forward body beside it costs gemm_kernel two VGPRs: it keeps its launch)
+    case K_LSTM_B: return (s.b <= LSTM_RIDE_H && lstm_small(s.count, s.a, s.b)) ? RIDE_LSTM : -1;
+    default: return -1;
     }
 }
 
@@ -1715,18 +1735,17 @@ void mst_plan::schedule() {
     // gradient arena, so a chunk can address it); mst_train_iteration then skips the separate clear
     if (K() == 1)
         for (const LstmDesc& l : lstms.host)
-            if (l.multi) { zero_all.push_back(ZeroChunk{act_top + l.xch_off, (int32_t)(2 * (2 * l.H + 8 * l.H)), 0}); tags_in_zero = true; }
+            if (l.multi) { zero_all.push_back(ZeroChunk{arena(SP_TMP) - arena(SP_GRAD) + l.xch_off, (int32_t)(2 * (2 * l.H + 8 * l.H)), 0}); tags_in_zero = true; }
     find_zero_ride();
     if (!tiled()) return;
     // ---- one train iteration of a tiled plan as phases that end at an exchange
     {   // loss partial sums (7 per note tensor, one row per workgroup) -> 16 floats that the ranks sum
         const bool U = d.has_unpitched != 0;
         loss_sum_off = tmp(16);
-        const int64_t np = (int64_t)P() * NF * NPN, nu = U ? (int64_t)Q() * NF * NUN : 0;
-        FoldDesc f{}; f.space = SP_TMP; f.part_off = loss_scratch; f.nrows = loss_blocks(np); f.row_stride = 8; f.ncols = 7; f.col_stride = 1;
+        FoldDesc f{}; f.space = SP_TMP; f.part_off = loss_scratch; f.nrows = loss_blocks(loss.np); f.row_stride = 8; f.ncols = 7; f.col_stride = 1;
         f.sum_off = loss_sum_off;
         loss_fold[0] = (int)folds.host.size(); folds.host.push_back(f);
-        f.part_off = loss_scratch + (mst_loss_scratch_floats() - 64) / 2; f.nrows = U ? loss_blocks(nu) : 1; f.sum_off = loss_sum_off + 8;
+        f.part_off = loss_scratch + (mst_loss_scratch_floats() - 64) / 2; f.nrows = U ? loss_blocks(loss.nu) : 1; f.sum_off = loss_sum_off + 8;
         loss_fold[1] = (int)folds.host.size(); folds.host.push_back(f);
     }
     auto mk = [](int what, int pass, int begin, int end) { Phase ph{}; ph.what = what; ph.pass = pass; ph.begin = begin; ph.end = end; ph.nx = 0; return ph; };
@@ -1775,22 +1794,22 @@ void mst_plan::find_zero_ride() {
     const std::vector<Step>& L = sched_all[0];
     int first = -1;
     for (int i = 0; i < (int)L.size() && first < 0; ++i) {
-        if (L[i].carried) continue;
+        if (L[i].carrier >= 0) continue;
         if (tags_in_zero && L[i].kind == K_LSTM_T && lstms.sched[L[i].first].multi) continue;      // skipped: its only job was the clear
         first = i;
     }
     if (first < 0 || L[first].kind != K_GEMM) return;
-    // everything in absolute workspace floats: activations, then the gradient arena, then the scratch arena (make_bases)
-    auto base = [&](int space) -> int64_t { return space == SP_WS ? 0 : space == SP_GRAD ? (int64_t)K() * act_top : space == SP_TMP ? 2 * (int64_t)K() * act_top : -1; };
+    // everything in absolute workspace floats (arena)
     std::vector<Acc> acc;
     accesses(L[first], acc, true);
-    for (const Step& s : L) if (s.carried && s.lvl == L[first].lvl) accesses(s, acc, true);      // (a superset of what the launch carries)
+    // its riders are every carried step of its level: a whole-model list of a plan that mixes merges a level's K_GEMM steps into one
+    for (const int r : L[first].rider) if (r >= 0) accesses(L[r], acc, true);
     for (const Acc& a : acc) {
-        const int64_t ab = base(a.space);
+        const int64_t ab = arena(a.space);
         if (ab < 0) continue;                        // parameters and the borrowed inputs: not in the workspace
         for (int k = 0; k < K(); ++k)
             for (const ZeroChunk& c : zero_all) {
-                const int64_t lo = base(SP_GRAD) + shift(SP_GRAD, k) + c.off;
+                const int64_t lo = arena(SP_GRAD) + shift(SP_GRAD, k) + c.off;
                 if (ab + a.lo < lo + c.len && lo < ab + a.hi) return;
             }
     }
@@ -1870,7 +1889,7 @@ extern "C" mst_plan* mst_plan_create_ex(const mst_dims* d, const mst_plan_option
     if (p->d.clips < 1) p->d.clips = 1;
     build_params(*d, p->z, p->pt);
     p->build();
-    if (!p->err) p->schedule();
+    if (!p->err) { p->resolve_loss(); p->schedule(); }
     if (p->err) { *status = p->err; delete p; return nullptr; }
     int e = p->upload();
     if (e) { *status = e; mst_plan_destroy(p); return nullptr; }
@@ -1900,7 +1919,7 @@ extern "C" int32_t mst_plan_gemm_tile(const mst_plan* p) { return p ? (p->mfma ?
 
 extern "C" int32_t mst_plan_layout(const mst_plan* p, int64_t out[4]) {
     if (!p || !out) return MST_ERR_ARG;
-    out[0] = p->K(); out[1] = p->act_top; out[2] = p->tmp_top; out[3] = (int64_t)p->K() * p->act_top;
+    out[0] = p->K(); out[1] = p->act_top; out[2] = p->tmp_top; out[3] = p->arena(SP_GRAD);
     return MST_OK;
 }
 
@@ -1909,19 +1928,23 @@ extern "C" int32_t mst_plan_tensor(const mst_plan* p, const char* name, int64_t*
     auto it = p->named.find(name);
     if (it == p->named.end()) return MST_ERR_ARG;
     if (off) *off = it->second.off;
-    if (goff) *goff = (int64_t)p->K() * p->act_top + it->second.off;
+    if (goff) *goff = p->arena(SP_GRAD) + it->second.off;
     if (numel) *numel = (int64_t)it->second.rows * it->second.cols;
     return MST_OK;
+}
+
+// The steps of pass (mask, backward), in list order: what the report and instrumentation entry points index (run_pass filters in place)
+static std::vector<const Step*> steps_of(const mst_plan* p, int mask, int backward) {
+    std::vector<const Step*> steps;
+    for (auto& s : p->list(mask, backward)) if (s.stage & mask) steps.push_back(&s);
+    return steps;
 }
 
 extern "C" int32_t mst_plan_launch_count(const mst_plan* p, int32_t mask, int32_t backward) {
     if (!p) return MST_ERR_ARG;
     int n = 0;
-    for (auto& s : p->list(mask, backward)) {
-        if (!(s.stage & mask)) continue;
-        const int stage2 = (((s.kind == K_COMB_F || s.kind == K_COMB_B) && s.b != 0) || (s.kind == K_SEGRED && s.b > 0)) ? 1 : 0;
-        n += (s.carried ? 0 : 1) + stage2;          // a carried step's first stage is part of its level's GEMM launch
-    }
+    for (const Step* s : steps_of(p, mask, backward))
+        n += (s->carrier >= 0 ? 0 : 1) + (second_stage(*s) ? 1 : 0);          // a carried step's first stage is part of its carrier's launch
     if (backward) for (int s = 0; s < 3; ++s) if ((mask >> s) & 1) n += 1;
     return n;
 }
@@ -1931,32 +1954,36 @@ static Bases make_bases(const mst_plan* p, const float* params, float* gparams, 
     Bases b;
     b.p[SP_WS] = ws; b.p[SP_PAR] = const_cast<float*>(params); b.p[SP_GPAR] = gparams;
     b.p[SP_EXT0] = const_cast<float*>(pitched); b.p[SP_EXT1] = const_cast<float*>(unpitched);
-    b.p[SP_GRAD] = ws + (int64_t)p->K() * p->act_top; b.p[SP_TMP] = ws + 2 * (int64_t)p->K() * p->act_top;
+    b.p[SP_GRAD] = ws + p->arena(SP_GRAD); b.p[SP_TMP] = ws + p->arena(SP_TMP);
     b.flags = 0;
     return b;
 }
 
+// L: the scheduled list `s` is a step of (a carrier's riders are indices into it)
 // with_zero: the launch also clears the whole-model zero list (the K_GEMM step mst_plan::zero_ride names, in mst_train_iteration)
-static int run_step(const mst_plan* p, const Step& s, const Bases& b, hipStream_t st, bool with_zero = false) {
-    if (s.carried) return 0;              // launched by the K_GEMM step of its level
+static int run_step(const mst_plan* p, const std::vector<Step>& L, const Step& s, const Bases& b, hipStream_t st, bool with_zero = false) {
+    if (s.carrier >= 0) return 0;         // launched by its carrier
     switch (s.kind) {
     case K_GEMM: case K_GEMM_FOLD: {
-        const Riders& q = s.ride;
-        const int clips = s.count / s.b, gat_blocks = std::min(512, (q.gat_rows + GATHER_RIDER_ROWS - 1) / GATHER_RIDER_ROWS);
-        GemmRiders r{p->segreds.dev + q.seg_first, q.seg_members, q.seg_groups, p->gathers.dev + q.gat_first, q.gat_members, gat_blocks};
-        for (int large = 0; large < 2; ++large) {
-            const CombRide& c = q.comb[large];
-            if (!c.sites) continue;
-            r.comb[large] = {p->combines.dev + c.first, c.sites, large ? (c.nblk + 3) / 4 : 1,
-                             large ? (c.bwd ? COMB_RIDE_REDUCE : COMB_RIDE_SUMSQ) : (c.bwd ? COMB_RIDE_SMALL_B : COMB_RIDE_SMALL_F)};
-        }
-        if (q.lstm_members) { r.lstms = p->lstms.dev + q.lstm_first; r.lstm_members = q.lstm_members; r.lstm_blocks = (q.lstm_maxB + GEMM_THREADS / 64 - 1) / (GEMM_THREADS / 64);
-}
+        // an empty slot reads as a step without members: first 0, count 0, a 0, b 0
+        static const Step none{-1, 0, 0, 0, 0, 0};
+        auto rider = [&](int slot) -> const Step& { return s.rider[slot] >= 0 ? L[s.rider[slot]] : none; };
+        const Step &lstm = rider(RIDE_LSTM), &small = rider(RIDE_COMB_SMALL), &large = rider(RIDE_COMB_LARGE), &seg = rider(RIDE_SEGRED), &gat = rider(RIDE_GATHER);
+        const int clips = s.count / s.b, K = p->K();      // a rider's members per clip: count / K
+        // segment reduce: a = 256-lane groups per clip; gather: a = most rows of a member -> workgroups per member
+        GemmRiders r{p->segreds.dev + seg.first, seg.count / K, seg.a, p->gathers.dev + gat.first, gat.count / K,
+                     std::min(512, (gat.a + GATHER_RIDER_ROWS - 1) / GATHER_RIDER_ROWS)};
+        // combine: a = most 256-lane groups of a site, four per workgroup of a large site
+        if (small.count) r.comb[0] = {p->combines.dev + small.first, small.count / K, 1, small.kind == K_COMB_B ? COMB_RIDE_SMALL_B : COMB_RIDE_SMALL_F};
+        if (large.count) r.comb[1] = {p->combines.dev + large.first, large.count / K, (large.a + 3) / 4, large.kind == K_COMB_B ? COMB_RIDE_REDUCE : COMB_RIDE_SUMSQ};
+        // small backward LSTM: a = most sequences of a member, one per wave
+        if (lstm.count) { r.lstms = p->lstms.dev + lstm.first; r.lstm_members = lstm.count / K; r.lstm_blocks = (lstm.a + GEMM_THREADS / 64 - 1) / (GEMM_THREADS / 64); }
         if (with_zero) { r.zero = p->d_zero_all; r.zero_chunks = (int)p->zero_all.size(); r.zero_stride = p->act_top; }
         int e = launch_gemm(p->gemms.dev + s.first, p->d_gemm_owner + s.c, s.b, s.a, clips, p->mfma, b, st, &r);
-        if (!e) e = launch_segred2(p->segreds.dev + q.seg_first, q.seg_members * clips, q.seg_stage2, b, st);
-        if (!e && q.comb[1].sites)       // the second phase of a carried large combine: directly behind the carrier
-            e = launch_combine_phase(p->combines.dev + q.comb[1].first, q.comb[1].nblk, q.comb[1].bwd ? 3 : 1, b, st, q.comb[1].sites * clips, 1, 1);
+        // second stages of what it carried: directly behind the carrier
+        if (!e && second_stage(seg)) e = launch_segred2(p->segreds.dev + seg.first, seg.count / K * clips, seg.b, b, st);
+        if (!e && second_stage(large))
+            e = launch_combine_phase(p->combines.dev + large.first, large.a, large.kind == K_COMB_B ? 3 : 1, b, st, large.count / K * clips, 1, 1);
         return e;
     }
     case K_GATHER: return launch_gather(p->gathers.dev + s.first, s.count, s.a, b, st);
@@ -2025,7 +2052,7 @@ static int run_pass(const mst_plan* p, const std::vector<Step>& list, int mask, 
             for (int w = 0; w < 3; ++w)
                 if (s.wait[w] >= 0 && hipStreamWaitEvent(st, ss->ev[s.wait[w]], 0) != hipSuccess) return MST_ERR_LAUNCH;
         }
-        int e = run_step(p, s, b, st, zero_step >= 0 && &s == &list[zero_step]);
+        int e = run_step(p, list, s, b, st, zero_step >= 0 && &s == &list[zero_step]);
         if (e) return e < 0 ? e : MST_ERR_LAUNCH;
         if (ss && s.signal >= 0 && hipEventRecord(ss->ev[s.signal], st) != hipSuccess) return MST_ERR_LAUNCH;
     }
@@ -2059,7 +2086,7 @@ extern "C" int32_t mst_plan_status(const mst_plan* p, float* ws, int32_t clear, 
 extern "C" int32_t mst_zero_grads(const mst_plan* p, int32_t mask, float* ws, mst_stream stream) {
     if (!p || !ws) return MST_ERR_ARG;
     // only the ranges the first-writer analysis could not prove written before they are read / accumulated into
-    float* g = ws + (int64_t)p->K() * p->act_top;
+    float* g = ws + p->arena(SP_GRAD);
     if ((mask & MST_STAGE_ALL) == MST_STAGE_ALL)
         return launch_zero(p->d_zero_all, (int)p->zero_all.size(), p->K(), g, p->act_top, (hipStream_t)stream) ? MST_ERR_LAUNCH : MST_OK;
     for (int s = 0; s < 3; ++s) {
@@ -2094,6 +2121,32 @@ extern "C" int32_t mst_backward(const mst_plan* p, int32_t mask, const float* pa
     return backward_impl(p, mask, params, gparams, ws, pitched, unpitched, stream, 0);
 }
 
+// The loss kernels with their operands from the plan's LossOps.  LOSS_WHOLE: every clip's losses in one go; a tiled plan runs the
+// two halves instead, around the ranks' sum of the partials: LOSS_PARTIALS, LOSS_TAIL
+enum { LOSS_WHOLE, LOSS_PARTIALS, LOSS_TAIL };
+static int loss_forward(const mst_plan* p, int what, float* ws, const float* pitched, const float* unpitched, float* losses, hipStream_t st) {
+    const mst_plan::LossOps& o = p->loss;
+    const bool U = p->d.has_unpitched != 0;
+    const float *pp = ws + o.pp, *up = U ? ws + o.up : nullptr, *ut = U ? unpitched : nullptr;
+    float* scratch = ws + p->arena(SP_TMP) + p->loss_scratch;
+    if (what == LOSS_PARTIALS) return loss_fwd_partials(pp, pitched, o.np, up, ut, o.nu, scratch, st);
+    if (what == LOSS_TAIL)
+        return loss_fwd_tail(o.np, o.nu, U ? 1 : 0, ws + o.il, ws + o.it, p->z.NI, ws + o.mlg, ws + o.mt, ws + o.bp, ws + o.bt, 1,
+                             ws + o.losses, ws + o.saved, scratch, st, ws + o.gl, losses);
+    return loss_fwd_batched(pp, pitched, o.np, up, ut, o.nu, ws + o.il, ws + o.it, p->z.NI, ws + o.mlg, ws + o.mt, ws + o.bp, ws + o.bt, 1,
+                            ws + o.losses, ws + o.saved, scratch, p->loss_batch(), st, ws + o.gl, losses);
+}
+// pitched_grad: dL/d pitched_pred is written too; info_scale: see loss_bwd_batched
+static int loss_backward(const mst_plan* p, float* ws, const float* pitched, const float* unpitched, bool pitched_grad, const LossBatch& lb,
+                         float info_scale, hipStream_t st) {
+    const mst_plan::LossOps& o = p->loss;
+    const bool U = p->d.has_unpitched != 0;
+    float* g = ws + p->arena(SP_GRAD);
+    return loss_bwd_batched(ws + o.pp, pitched, o.np, U ? ws + o.up : nullptr, U ? unpitched : nullptr, o.nu, ws + o.il, ws + o.it, p->z.NI,
+                            ws + o.mlg, ws + o.mt, ws + o.bp, ws + o.bt, ws + o.saved, ws + o.gl, pitched_grad ? g + o.pp : nullptr,
+                            U ? g + o.up : nullptr, g + o.il, g + o.mlg, g + o.bp, lb, st, info_scale);
+}
+
 extern "C" int32_t mst_train_iteration(const mst_plan* p, const float* params, float* gparams, float* ws,
                                        const float* pitched, const float* unpitched, float* losses, mst_stream stream) {
     if (!p || !params || !gparams || !ws || !pitched) return MST_ERR_ARG;
@@ -2104,24 +2157,9 @@ extern "C" int32_t mst_train_iteration(const mst_plan* p, const float* params, f
     if (p->d.has_unpitched && !unpitched) return MST_ERR_ARG;
     e = run_pass(p, p->list(MST_STAGE_ALL, 0), MST_STAGE_ALL, make_bases(p, params, nullptr, ws, pitched, unpitched), st, p->tags_in_zero, p->zero_ride);
     if (e) return e;
-    const bool U = p->d.has_unpitched != 0;
-    const int K = p->K();
-    float* g = ws + (int64_t)K * p->act_top;
-    auto at = [&](const char* n) { return p->named.at(n).off; };
-    const int64_t np = (int64_t)p->P() * NF * NPN, nu = U ? (int64_t)p->Q() * NF * NUN : 0;
-    float* lscratch = ws + 2 * (int64_t)K * p->act_top + p->loss_scratch;
-    const LossBatch lb = {K, p->act_top, p->act_top, p->tmp_top, p->ext0_stride(), p->ext1_stride()};
-    e = loss_fwd_batched(ws + at("pitched_pred"), pitched, np, U ? ws + at("unpitched_pred") : nullptr, U ? unpitched : nullptr,
-                         nu, ws + at("instruments_pred"), ws + at("used_instruments"), p->z.NI, ws + at("mode_pred"),
-                         ws + at("mode"), ws + at("bpm_pred"), ws + at("bpm_target"), 1, ws + p->t_losses.off,
-                         ws + p->t_saved.off, lscratch, lb, st, ws + p->t_gl.off, losses);
+    e = loss_forward(p, LOSS_WHOLE, ws, pitched, unpitched, losses, st);
     if (e) return e;
-    e = loss_bwd_batched(ws + at("pitched_pred"), pitched, np, U ? ws + at("unpitched_pred") : nullptr, U ? unpitched : nullptr,
-                         nu, ws + at("instruments_pred"), ws + at("used_instruments"), p->z.NI, ws + at("mode_pred"),
-                         ws + at("mode"), ws + at("bpm_pred"), ws + at("bpm_target"), ws + p->t_saved.off,
-                         ws + p->t_gl.off, nullptr /* the applier's backward kernel derives dL/d pitched_pred itself */,
-                         U ? g + at("unpitched_pred") : nullptr,
-                         g + at("instruments_pred"), g + at("mode_pred"), g + at("bpm_pred"), lb, st);
+    e = loss_backward(p, ws, pitched, unpitched, false /* the applier's backward kernel derives dL/d pitched_pred itself */, p->loss_batch(), 1.f, st);
     if (e) return e;
     e = backward_impl(p, MST_STAGE_ALL, params, gparams, ws, pitched, unpitched, stream, MST_BF_LOSS_FUSED);
     if (e) return e;
@@ -2151,28 +2189,22 @@ extern "C" int32_t mst_eval_iteration(const mst_plan* p, const float* params, fl
     if (e) return e;
     const bool U = p->d.has_unpitched != 0;
     const int K = p->K(), C = p->d.C;
-    auto at = [&](const char* n) { return p->named.at(n).off; };
-    const int64_t np = (int64_t)p->P() * NF * NPN, nu = U ? (int64_t)p->Q() * NF * NUN : 0;
-    float* lscratch = ws + 2 * (int64_t)K * p->act_top + p->loss_scratch;
-    const LossBatch lb = {K, p->act_top, p->act_top, p->tmp_top, p->ext0_stride(), p->ext1_stride()};
-    e = loss_fwd_batched(ws + at("pitched_pred"), pitched, np, U ? ws + at("unpitched_pred") : nullptr, U ? unpitched : nullptr,
-                         nu, ws + at("instruments_pred"), ws + at("used_instruments"), p->z.NI, ws + at("mode_pred"),
-                         ws + at("mode"), ws + at("bpm_pred"), ws + at("bpm_target"), 1, ws + p->t_losses.off,
-                         ws + p->t_saved.off, lscratch, lb, st, ws + p->t_gl.off, losses);
+    const mst_plan::LossOps& o = p->loss;
+    e = loss_forward(p, LOSS_WHOLE, ws, pitched, unpitched, losses, st);
     if (e) return e;
     EvalMetricsArgs a{};
-    a.part_p = scratch; a.slices_p = eval_slices(p, true); a.cells_p = np / C;
-    e = launch_roll_metrics(ws + at("pitched_pred"), pitched, (int64_t)K * C, a.cells_p, NPF, C, p->act_top, p->ext0_stride(), scratch, st);
+    a.part_p = scratch; a.slices_p = eval_slices(p, true); a.cells_p = o.np / C;
+    e = launch_roll_metrics(ws + o.pp, pitched, (int64_t)K * C, a.cells_p, NPF, C, p->act_top, p->ext0_stride(), scratch, st);
     if (e) return e;
     if (U) {
         void* su = (char*)scratch + 32 * (int64_t)K * C * a.slices_p;
-        a.part_u = su; a.slices_u = eval_slices(p, false); a.cells_u = nu;
-        e = launch_roll_metrics(ws + at("unpitched_pred"), unpitched, K, nu, NUF, 1, p->act_top, p->ext1_stride(), su, st);
+        a.part_u = su; a.slices_u = eval_slices(p, false); a.cells_u = o.nu;
+        e = launch_roll_metrics(ws + o.up, unpitched, K, o.nu, NUF, 1, p->act_top, p->ext1_stride(), su, st);
         if (e) return e;
     }
     a.C = C; a.ni = p->z.NI;
-    a.il = ws + at("instruments_pred"); a.it = ws + at("used_instruments"); a.mlg = ws + at("mode_pred"); a.mt = ws + at("mode");
-    a.bp = ws + at("bpm_pred"); a.bt = ws + at("bpm_target"); a.ws_stride = p->act_top; a.out = metrics;
+    a.il = ws + o.il; a.it = ws + o.it; a.mlg = ws + o.mlg; a.mt = ws + o.mt;
+    a.bp = ws + o.bp; a.bt = ws + o.bt; a.ws_stride = p->act_top; a.out = metrics;
     return launch_eval_metrics_finish(a, K, st);
 }
 
@@ -2199,48 +2231,35 @@ extern "C" int32_t mst_tiled_phase(const mst_plan* p, int32_t phase, const float
     Bases b = make_bases(p, params, gparams, ws, pitched, unpitched);
     b.flags |= MST_BF_ALL_STAGES;
     const bool U = p->d.has_unpitched != 0;
-    float* g = ws + p->act_top;
-    auto at = [&](const char* n) { return p->named.at(n).off; };
-    const int64_t np = (int64_t)p->P() * NF * NPN, nu = U ? (int64_t)p->Q() * NF * NUN : 0;
-    float* lscratch = ws + 2 * p->act_top + p->loss_scratch;
     if (phase == 0) {
-        if (launch_zero(p->d_zero_all, (int)p->zero_all.size(), 1, g, p->act_top, st)) return MST_ERR_LAUNCH;
+        if (launch_zero(p->d_zero_all, (int)p->zero_all.size(), 1, ws + p->arena(SP_GRAD), p->act_top, st)) return MST_ERR_LAUNCH;
         if (launch_zero(p->d_zero_fwd, (int)p->zero_fwd.size(), 1, ws, p->act_top, st)) return MST_ERR_LAUNCH;
     }
     if (ph.what == 0) {
         const std::vector<Step>& L = p->sched_all[ph.pass];
         for (int i = ph.begin; i < ph.end; ++i) {
             if (L[i].kind == K_XCHG) continue;          // an earlier exchange of the level this phase ends at: delivered with the others
-            int e = run_step(p, L[i], b, st);
+            int e = run_step(p, L, L[i], b, st);
             if (e) return e < 0 ? e : MST_ERR_LAUNCH;
         }
         if (ph.pass == 1 && phase == (int)p->phases.size() - 1)
             for (int s = 2; s >= 0; --s)
                 if (launch_slab_reduce(p->d_slabs[s], p->d_slab_blocks[s], (int)p->slab_blocks[s].size(), b, st)) return MST_ERR_LAUNCH;
     } else if (ph.what == 1) {
-        int e = loss_fwd_partials(ws + at("pitched_pred"), pitched, np, U ? ws + at("unpitched_pred") : nullptr, U ? unpitched : nullptr, nu,
-                                  lscratch, st);
+        int e = loss_forward(p, LOSS_PARTIALS, ws, pitched, unpitched, losses, st);
         if (e) return e;
         if (launch_fold(p->folds.dev + p->loss_fold[0], 0, b, st) || (U && launch_fold(p->folds.dev + p->loss_fold[1], 0, b, st))) return MST_ERR_LAUNCH;
     } else {
         if (launch_fold(p->folds.dev + p->loss_fold[0], 1, b, st) || (U && launch_fold(p->folds.dev + p->loss_fold[1], 1, b, st))) return MST_ERR_LAUNCH;
-        int e = loss_fwd_tail(np, nu, U ? 1 : 0, ws + at("instruments_pred"), ws + at("used_instruments"), p->z.NI, ws + at("mode_pred"),
-                              ws + at("mode"), ws + at("bpm_pred"), ws + at("bpm_target"), 1, ws + p->t_losses.off, ws + p->t_saved.off,
-                              lscratch, st, ws + p->t_gl.off, losses);
+        int e = loss_forward(p, LOSS_TAIL, ws, pitched, unpitched, losses, st);
         if (e) return e;
-        const LossBatch lb = {1, 0, 0, 0, 0, 0};
-        e = loss_bwd_batched(ws + at("pitched_pred"), pitched, np, U ? ws + at("unpitched_pred") : nullptr, U ? unpitched : nullptr, nu,
-                             ws + at("instruments_pred"), ws + at("used_instruments"), p->z.NI, ws + at("mode_pred"), ws + at("mode"),
-                             ws + at("bpm_pred"), ws + at("bpm_target"), ws + p->t_saved.off, ws + p->t_gl.off, g + at("pitched_pred"),
-                             U ? g + at("unpitched_pred") : nullptr, g + at("instruments_pred"), g + at("mode_pred"), g + at("bpm_pred"),
-                             lb, st, is_root ? 1.f : 0.f);
+        e = loss_backward(p, ws, pitched, unpitched, true, LossBatch{1, 0, 0, 0, 0, 0}, is_root ? 1.f : 0.f, st);
         if (e) return e;
     }
     *nx = ph.nx;
     for (int q = 0; q < ph.nx; ++q) {
         const mst_plan::Xchg& x = p->xchgs[ph.xchg[q]];
-        const int64_t base = x.space == SP_WS ? 0 : (x.space == SP_GRAD ? p->act_top : 2 * p->act_top);
-        xoff[q] = base + x.off; xlen[q] = x.len;
+        xoff[q] = p->arena(x.space) + x.off; xlen[q] = x.len;
     }
     return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
 }
@@ -2340,8 +2359,8 @@ extern "C" int64_t mst_plan_zero_floats(const mst_plan* p, int32_t mask) {
 extern "C" int32_t mst_plan_step_carried(const mst_plan* p, int32_t mask, int32_t backward, int32_t* carried) {
     if (!p || !carried) return MST_ERR_ARG;
     int n = 0;
-    for (auto& s : p->list(mask, backward))
-        if (s.stage & mask) carried[n++] = (!s.carried || (s.kind != K_GATHER && s.kind != K_SEGRED)) ? 0 : ((s.kind == K_SEGRED && s.b > 0) ? 2 : 1);
+    for (const Step* s : steps_of(p, mask, backward))
+        carried[n++] = (s->carrier < 0 || (s->kind != K_GATHER && s->kind != K_SEGRED)) ? 0 : (second_stage(*s) ? 2 : 1);
     return n;
 }
 
@@ -2350,11 +2369,8 @@ extern "C" int32_t mst_plan_step_carried(const mst_plan* p, int32_t mask, int32_
 extern "C" int32_t mst_plan_step_riders(const mst_plan* p, int32_t mask, int32_t backward, int32_t* out) {
     if (!p || !out) return MST_ERR_ARG;
     int n = 0;
-    for (auto& s : p->list(mask, backward)) {
-        if (!(s.stage & mask)) continue;
-        const bool two = (s.kind == K_SEGRED && s.b > 0) || ((s.kind == K_COMB_F || s.kind == K_COMB_B) && s.b != 0);
-        out[n++] = (!s.carried || s.kind == K_LSTM_F || s.kind == K_LSTM_B) ? 0 : (two ? 2 : 1);      // LSTM steps: mst_plan_step_carrier
-    }
+    for (const Step* s : steps_of(p, mask, backward))
+        out[n++] = (s->carrier < 0 || s->kind == K_LSTM_F || s->kind == K_LSTM_B) ? 0 : (second_stage(*s) ? 2 : 1);      // LSTM steps: mst_plan_step_carrier
     return n;
 }
 
@@ -2362,27 +2378,11 @@ extern "C" int32_t mst_plan_step_riders(const mst_plan* p, int32_t mask, int32_t
 extern "C" int32_t mst_plan_step_carrier(const mst_plan* p, int32_t mask, int32_t backward, int32_t* out) {
     if (!p || !out) return MST_ERR_ARG;
     const std::vector<Step>& L = p->list(mask, backward);
+    const std::vector<const Step*> steps = steps_of(p, mask, backward);
     std::vector<int> pos(L.size(), -1);             // list index -> index among the steps of `mask`
     int n = 0;
-    for (size_t i = 0; i < L.size(); ++i) if (L[i].stage & mask) pos[i] = n++;
-    for (size_t i = 0; i < L.size(); ++i) {
-        const Step& s = L[i];
-        if (pos[i] < 0) continue;
-        int at = -1;
-        if (s.carried)
-            for (size_t c = 0; c < L.size() && at < 0; ++c) {
-                const Step& g = L[c];
-                if (g.kind != K_GEMM || g.lvl != s.lvl) continue;
-                const Riders& q = g.ride;
-                const bool mine = (s.kind == K_GATHER && q.gat_members && q.gat_first == s.first) ||
-                                  (s.kind == K_SEGRED && q.seg_members && q.seg_first == s.first) ||
-                                  ((s.kind == K_COMB_F || s.kind == K_COMB_B) && q.comb[s.b != 0].sites && q.comb[s.b != 0].first == s.first &&
-                                   q.comb[s.b != 0].bwd == (s.kind == K_COMB_B)) ||
-                                  (s.kind == K_LSTM_B && q.lstm_members && q.lstm_first == s.first);
-                if (mine) at = pos[c];
-            }
-        out[pos[i]] = at;
-    }
+    for (const Step* s : steps) pos[s - L.data()] = n++;
+    for (const Step* s : steps) *out++ = s->carrier < 0 ? -1 : pos[s->carrier];
     return n;
 }
 
@@ -2392,7 +2392,7 @@ extern "C" int32_t mst_plan_set_lstm_small(mst_plan* p, int32_t on) {
     for (int pass = 0; pass < 2; ++pass)
         for (const std::vector<Step>* L : {&p->sched[pass], &p->sched_all[pass]})
             for (const Step& s : *L)
-                if ((s.kind == K_LSTM_F || s.kind == K_LSTM_B) && s.carried) return MST_ERR_UNSUPPORTED;      // run inside a gemm_kernel launch
+                if ((s.kind == K_LSTM_F || s.kind == K_LSTM_B) && s.carrier >= 0) return MST_ERR_UNSUPPORTED;      // run inside a gemm_kernel launch
     p->lstm_small_on = on ? 1 : 0;          // read by run_step at each launch
     return MST_OK;
 }
@@ -2400,20 +2400,15 @@ extern "C" int32_t mst_plan_set_lstm_small(mst_plan* p, int32_t on) {
 extern "C" int32_t mst_plan_zero_rides(const mst_plan* p) { return !p ? MST_ERR_ARG : (p->zero_ride >= 0 ? 1 : 0); }
 
 extern "C" int32_t mst_plan_step_count(const mst_plan* p, int32_t mask, int32_t backward) {
-    if (!p) return MST_ERR_ARG;
-    int n = 0;
-    for (auto& s : p->list(mask, backward)) if (s.stage & mask) ++n;
-    return n;
+    return p ? (int32_t)steps_of(p, mask, backward).size() : MST_ERR_ARG;
 }
 
 // shape of step i of a pass: GEMM {M,N,K,ksplit} of its first descriptor (+count), LSTM {B,S,H,count},
 // segment-reduce {nidx max, width, rows, count}; then the member count, the step kind, its dependency level and its chain (-1: none)
 extern "C" int32_t mst_plan_step_info(const mst_plan* p, int32_t mask, int32_t backward, int32_t* info /* 8 per step */) {
     if (!p || !info) return MST_ERR_ARG;
-    std::vector<const Step*> steps;
-    for (auto& s : p->list(mask, backward)) if (s.stage & mask) steps.push_back(&s);
     int idx = 0;
-    for (const Step* s : steps) {
+    for (const Step* s : steps_of(p, mask, backward)) {
         int32_t* o = info + 8 * idx++;
         o[0] = o[1] = o[2] = o[3] = 0; o[4] = s->count; o[5] = s->kind; o[6] = s->lvl; o[7] = s->chain;
         if (s->kind == K_GEMM || s->kind == K_GEMM_FOLD) { const GemmDesc& g = p->gemms.sched[s->first]; o[0] = g.M; o[1] = g.N; o[2] = g.K; o[3] = g.ksplit; }
@@ -2429,20 +2424,17 @@ extern "C" int32_t mst_plan_step_info(const mst_plan* p, int32_t mask, int32_t b
 // members of GEMM step i of a pass, one clip's worth: {M, N, K, ksplit, fold_rows, workgroups} each (tools/step_profile.py)
 extern "C" int32_t mst_plan_step_gemms(const mst_plan* p, int32_t mask, int32_t backward, int32_t step, int32_t* out, int32_t cap) {
     if (!p || !out) return MST_ERR_ARG;
-    int idx = 0;
-    for (auto& s : p->list(mask, backward)) {
-        if (!(s.stage & mask)) continue;
-        if (idx++ != step) continue;
-        if (s.kind != K_GEMM && s.kind != K_GEMM_FOLD) return 0;
-        int n = 0;
-        for (int q = 0; q < s.b && n < cap; ++q, ++n) {
-            const GemmDesc& g = p->gemms.sched[s.first + q];
-            int32_t* o = out + 6 * n;
-            o[0] = g.M; o[1] = g.N; o[2] = g.K; o[3] = g.ksplit; o[4] = g.fold_rows; o[5] = gemm_blocks(g, p->mfma);
-        }
-        return n;
+    const std::vector<const Step*> steps = steps_of(p, mask, backward);
+    if (step < 0 || step >= (int)steps.size()) return MST_ERR_ARG;
+    const Step& s = *steps[step];
+    if (s.kind != K_GEMM && s.kind != K_GEMM_FOLD) return 0;
+    int n = 0;
+    for (int q = 0; q < s.b && n < cap; ++q, ++n) {
+        const GemmDesc& g = p->gemms.sched[s.first + q];
+        int32_t* o = out + 6 * n;
+        o[0] = g.M; o[1] = g.N; o[2] = g.K; o[3] = g.ksplit; o[4] = g.fold_rows; o[5] = gemm_blocks(g, p->mfma);
     }
-    return MST_ERR_ARG;
+    return n;
 }
 
 extern "C" int32_t mst_plan_time_steps(const mst_plan* p, int32_t mask, int32_t backward, const float* params, float* gparams,
@@ -2455,23 +2447,18 @@ extern "C" int32_t mst_plan_time_steps(const mst_plan* p, int32_t mask, int32_t 
     if ((mask & MST_STAGE_ALL) == MST_STAGE_ALL) b.flags |= MST_BF_ALL_STAGES;
     hipEvent_t e0, e1;
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return MST_ERR_ALLOC;
-    std::vector<const Step*> steps;
-    for (auto& s : p->list(mask, backward)) if (s.stage & mask) steps.push_back(&s);
+    const std::vector<Step>& L = p->list(mask, backward);
     int idx = 0;
-    for (const Step* s : steps) {
-        if (s->carried) {                             // timed inside its level's GEMM step: 0 ms here, with its own work
-            ms[idx] = 0.f; kind[idx] = s->kind;
-            step_cost(p, *s, &flops[idx], &bytes[idx]);
-            ++idx;
-            continue;
-        }
-        run_step(p, *s, b, st);                       // warm
-        hipEventRecord(e0, st);
-        for (int r = 0; r < reps; ++r) run_step(p, *s, b, st);
-        hipEventRecord(e1, st);
-        hipEventSynchronize(e1);
+    for (const Step* s : steps_of(p, mask, backward)) {
         float t = 0.f;
-        hipEventElapsedTime(&t, e0, e1);
+        if (s->carrier < 0) {                         // a carried step is timed inside its carrier's: 0 ms here, with its own work
+            run_step(p, L, *s, b, st);                // warm
+            hipEventRecord(e0, st);
+            for (int r = 0; r < reps; ++r) run_step(p, L, *s, b, st);
+            hipEventRecord(e1, st);
+            hipEventSynchronize(e1);
+            hipEventElapsedTime(&t, e0, e1);
+        }
         ms[idx] = t / reps; kind[idx] = s->kind == K_GEMM_FOLD ? K_GEMM : s->kind;      // same kernel
         step_cost(p, *s, &flops[idx], &bytes[idx]);
         ++idx;
