@@ -349,6 +349,54 @@ int64_t mst_eval_scratch_bytes(const mst_plan* p);
 int32_t mst_eval_iteration(const mst_plan* p, const float* params, float* ws, const float* pitched,
                            const float* unpitched, float* losses, double* metrics, void* scratch, mst_stream stream);
 
+/* ---- windowed evaluation: a held-out round over a fixed set of windows of resident songs is N replays of one graph —
+ * mst_clip_window x 2, mst_window_inputs, mst_eval_iteration, mst_eval_accumulate — and ONE download of 41 doubles.  No reference
+ * counterpart: the reference has no validation.  Both entry points are enqueue-only on `stream` (no allocation, no host
+ * synchronisation, capturable as a single chain), one launch each, without atomics and without a workgroup waiting for another:
+ * the same bits on every run.
+ *
+ * mst_window_inputs: rows of a device table into per-clip workspace slots.  `table` is table_rows x row_floats floats (a song's
+ * small inputs — mode, bpm, instrument features, used instruments, bpm target — are one row); rows[k] (a DEVICE array of n_clips
+ * int32, read ON THE DEVICE as mst_clip_window reads its descriptors: a captured launch serves other songs) names clip k's row;
+ * `fields` (HOST memory, read at the call) lists up to MST_ROW_FIELDS pieces of a row and where each goes.  For clip k, field
+ * f < fields->n and i < len[f]:
+ *     ws[dst[f] + k * clip_stride + i] = table[rows[k] * row_floats + src[f] + i]          copied bit for bit
+ * A rows[k] outside [0, table_rows) writes quiet NaNs (0x7fc00000) into that clip's fields instead — the mistake shows in the
+ * losses rather than leaving stale inputs — and the table is never read outside its rows.  Every float of the named destinations
+ * is written exactly once and nothing else is written; keeping the destinations disjoint is the caller's business (a plan's
+ * slots are: mst_plan_tensor, mst_plan_layout).  table and ws need float alignment only.  A field of length 0 names nothing.
+ * MST_ERR_ARG, and nothing is launched: null pointer, n_clips / table_rows / row_floats < 1, fields->n outside 1..8, a negative
+ * src, len or dst, src + len > row_floats, clip_stride < 0, table / ws not 4-byte aligned. */
+#define MST_ROW_FIELDS 8
+typedef struct { int32_t n; int32_t src[MST_ROW_FIELDS], len[MST_ROW_FIELDS]; int64_t dst[MST_ROW_FIELDS]; } mst_row_fields;
+int32_t mst_window_inputs(const float* table, int32_t table_rows, int32_t row_floats,
+                          const int32_t* rows /* DEVICE, n_clips */, int32_t n_clips,
+                          const mst_row_fields* fields /* HOST, read at the call */,
+                          int64_t clip_stride, float* ws, mst_stream stream);
+
+/* mst_eval_accumulate: acc += the batch that mst_eval_iteration just left in `losses` (n_clips x MST_N_LOSSES) and `metrics`
+ * (n_clips x (channels + 2) records of MST_METRIC_WORDS doubles).  Only the first min(max(*live, 0), n_clips) clips count
+ * (live: one DEVICE int32, read on the device, so one graph serves full batches and a round's padded last one; NULL = all).
+ * The caller zeroes acc once per round.  Words of acc:
+ *   [0]        clips counted
+ *   [1]        counted clips whose MST_L_U_TOTAL is not NaN (clips with percussion)
+ *   [2 + i]    sum of loss leaf i, each float widened to double; the four leaves MST_L_U_TOTAL .. MST_L_U_DURATION are added only
+ *              for the clips counted in [1]; any other NaN is a real one and propagates (style.metrics.nanmean_leaves' rule)
+ *   [17 .. 25) the pitched record, summed over the counted clips and their `channels` records
+ *   [25 .. 33) the unpitched record, summed over the counted clips
+ *   [33 .. 41) the song-info record, summed over the counted clips, with 1 added to a record's word 7 before it is added: the
+ *              `songs` denominator
+ * Every word is a left-to-right float64 sum that starts from the word's value on entry and takes its terms in the order clip
+ * 0, 1, ... and, within a clip, channel 0, 1, ...: the bits a host loop of double additions in that order gives.  A word without
+ * terms (*live <= 0) keeps its bits.  One workgroup of 64 lanes, lane w < 41 owns word w; nothing outside acc[0, 41) is written.
+ * MST_ERR_ARG: a null pointer other than live, n_clips < 1, channels < 1, metrics / acc not 8-byte aligned. */
+#define MST_EVAL_ACC_WORDS (2 + MST_N_LOSSES + 3 * MST_METRIC_WORDS)   /* 41 doubles */
+int32_t mst_eval_accumulate(const float* losses   /* n_clips x MST_N_LOSSES */,
+                            const double* metrics /* n_clips x (channels + 2) x MST_METRIC_WORDS, mst_eval_iteration's */,
+                            int32_t n_clips, int32_t channels,
+                            const int32_t* live   /* DEVICE, one int32, or NULL = all */,
+                            double* acc /* MST_EVAL_ACC_WORDS, 8-byte aligned */, mst_stream stream);
+
 /* ---- instrumentation (bench.py only; synchronises on HIP events, never used for training):
  * average duration of every launch step of a pass, with its algorithmic FLOPs and bytes.
  * kind: 0 gemm, 1 gather, 2 segment-reduce, 3/4 lstm fwd/bwd, 5/6 combine fwd/bwd, 7/8 melody notes, 9/10 applier notes,

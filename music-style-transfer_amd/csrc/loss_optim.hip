@@ -1360,3 +1360,176 @@ extern "C" int32_t mst_roll_metrics(const float* pred, const float* target, int6
                        mst_roll_slices(group_cells), group_cells, out);
     return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
 }
+
+// ------------------------------------------------------------------ windowed evaluation (mst_window_inputs, mst_eval_accumulate)
+// The two small launches that let a held-out round stay on the device: the K clips' small inputs gathered out of the song
+// table by row indices read HERE (a captured launch serves other songs), and the batch folded into the round's 41 doubles.
+// Both are latency-bound; what they owe is exactness: bit copies, one fixed summation order, no atomics.
+#define WI_THREADS 256
+#define WI_CHUNK 1024        // floats of a clip's concatenated fields one workgroup copies
+
+struct WindowInputsArgs {
+    int32_t n, src[MST_ROW_FIELDS], len[MST_ROW_FIELDS], at[MST_ROW_FIELDS + 1];     // at[f]: field f's first float in the concatenation
+    int64_t dst[MST_ROW_FIELDS];
+};
+
+// workgroup b: chunk b % chunks of clip b / chunks.  The row index is one load per workgroup (every lane reads the same
+// address); lanes stride over the chunk's floats.  Words are moved as uint32: a bit copy whatever the float holds.
+__global__ __launch_bounds__(WI_THREADS) void window_inputs_kernel(const uint32_t* table, int table_rows, int row_floats, const int32_t* rows,
+                                                                   int chunks, WindowInputsArgs a, int64_t clip_stride, uint32_t* ws) {
+    const int k = blockIdx.x / chunks;
+    const int c0 = (blockIdx.x % chunks) * WI_CHUNK;
+    const int total = a.at[a.n];
+    const int c1 = c0 + WI_CHUNK < total ? c0 + WI_CHUNK : total;
+    const int row = MST_UNIFORM(rows[k]);
+    const bool ok = row >= 0 && row < table_rows;               // a row outside the table is never read: quiet NaNs instead
+    const uint32_t* src = table + (ok ? (int64_t)row * row_floats : 0);
+    uint32_t* dst = ws + (int64_t)k * clip_stride;
+    for (int e = c0 + (int)threadIdx.x; e < c1; e += WI_THREADS) {
+        int f = 0;
+        while (f + 1 < a.n && e >= a.at[f + 1]) ++f;
+        const int i = e - a.at[f];
+        dst[a.dst[f] + i] = ok ? src[a.src[f] + i] : 0x7fc00000u;
+    }
+}
+
+extern "C" int32_t mst_window_inputs(const float* table, int32_t table_rows, int32_t row_floats, const int32_t* rows, int32_t n_clips,
+                                     const mst_row_fields* fields, int64_t clip_stride, float* ws, mst_stream stream) {
+    if (!table || !rows || !fields || !ws || n_clips < 1 || table_rows < 1 || row_floats < 1 || clip_stride < 0 ||
+        fields->n < 1 || fields->n > MST_ROW_FIELDS || ((uintptr_t)table & 3) || ((uintptr_t)ws & 3))
+        return MST_ERR_ARG;
+    WindowInputsArgs a;
+    a.n = fields->n;
+    int64_t total = 0;
+    for (int f = 0; f < MST_ROW_FIELDS; ++f) {
+        const bool live = f < fields->n;
+        if (live && (fields->src[f] < 0 || fields->len[f] < 0 || fields->dst[f] < 0 ||
+                     (int64_t)fields->src[f] + fields->len[f] > row_floats))
+            return MST_ERR_ARG;
+        a.src[f] = live ? fields->src[f] : 0;
+        a.len[f] = live ? fields->len[f] : 0;
+        a.dst[f] = live ? fields->dst[f] : 0;
+        a.at[f] = (int32_t)total;
+        total += a.len[f];                                       // <= 8 * row_floats: may pass 2^31 only for a row of 2^28 floats
+        if (total >= ((int64_t)1 << 31)) return MST_ERR_ARG;
+    }
+    a.at[MST_ROW_FIELDS] = (int32_t)total;
+    for (int f = fields->n; f < MST_ROW_FIELDS; ++f) a.at[f] = (int32_t)total;
+    if (total == 0) return MST_OK;                               // every named field is empty: nothing to write
+    const int64_t chunks = (total + WI_CHUNK - 1) / WI_CHUNK;
+    if (chunks * n_clips > 0x7fffffff) return MST_ERR_ARG;
+    hipLaunchKernelGGL(window_inputs_kernel, dim3((unsigned)(chunks * n_clips)), dim3(WI_THREADS), 0, (hipStream_t)stream,
+                       (const uint32_t*)table, (int)table_rows, (int)row_floats, rows, (int)chunks, a, clip_stride, (uint32_t*)ws);
+    return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
+}
+
+// One 64-lane workgroup; lane w < MST_EVAL_ACC_WORDS owns acc[w] and adds its terms left to right in float64, starting from the
+// word's value on entry: clip 0, 1, ... and, for the pitched record, channel 0, 1, ... within a clip — the order of a host loop.
+// The loads do not depend on the add chains, the adds do, so the two are separated: all 64 lanes copy the next stretch of the
+// batch into LDS — plain consecutive addresses, EVAL_ACC_BATCH loads per lane in flight before the first is used — and the
+// owning lanes then walk it in order.  First the loss rows (lanes 0..16), then the records (lanes 17..40); a stretch is as many
+// whole loss rows, or whole records, as the 32 KB hold, so any n_clips and any channel count goes through the same code.
+// (A lane per word that loaded its own terms from global memory took 46 to 58 us for 64 clips of 4 channels whatever its
+// look-ahead: one wave issuing ~80 instructions of address arithmetic per term for the 256 terms of a pitched word.)
+#define EVAL_ACC_LDS 4096            // doubles: 512 records, or 8192 floats
+#define EVAL_ACC_BATCH 16
+#define EVAL_ACC_WALK 8              // LDS reads a walking lane issues together; the adds behind them are selects, not branches
+
+template <class V>
+__device__ __forceinline__ void eval_acc_stage(V* dst, const V* src, int count) {
+    for (int i0 = 0; i0 < count; i0 += 64 * EVAL_ACC_BATCH) {
+        V r[EVAL_ACC_BATCH];
+#pragma unroll
+        for (int q = 0; q < EVAL_ACC_BATCH; ++q) {
+            const int i = i0 + q * 64 + (int)threadIdx.x;
+            r[q] = src[i < count ? i : count - 1];               // past the end: a valid address, the value is dropped
+        }
+#pragma unroll
+        for (int q = 0; q < EVAL_ACC_BATCH; ++q) {
+            const int i = i0 + q * 64 + (int)threadIdx.x;
+            if (i < count) dst[i] = r[q];
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void eval_accumulate_kernel(const float* losses, const double* metrics, int n_clips, int channels,
+                                                             const int32_t* live, double* acc) {
+    __shared__ double sm[EVAL_ACC_LDS];
+    float* sl = reinterpret_cast<float*>(sm);
+    const int w = threadIdx.x;
+    int n = live ? *live : n_clips;
+    n = n < 0 ? 0 : (n > n_clips ? n_clips : n);
+    if (n == 0) return;                                          // (every lane) acc + nothing: every word keeps its bits
+    const bool owner = w < MST_EVAL_ACC_WORDS;
+    const bool is_loss = w < 2 + MST_N_LOSSES;                   // [0], [1] and the leaf sums; the other owners hold record words
+    double sum = owner ? acc[w] : 0.0;
+
+    // ---- the loss rows: [0] and [1] count, [2 + i] adds leaf i
+    const bool count = w < 2;
+    const bool gated = w == 1 || (w >= 2 + MST_L_U_TOTAL && w <= 2 + MST_L_U_DURATION);     // only for clips with percussion
+    const int leaf = is_loss && !count ? w - 2 : 0;
+    const int rows_per = 2 * EVAL_ACC_LDS / MST_N_LOSSES;
+    for (int k0 = 0; k0 < n; k0 += rows_per) {
+        const int nk = n - k0 < rows_per ? n - k0 : rows_per;
+        eval_acc_stage(sl, losses + (int64_t)k0 * MST_N_LOSSES, nk * MST_N_LOSSES);
+        __syncthreads();
+        if (is_loss) {
+            for (int k1 = 0; k1 < nk; k1 += EVAL_ACC_WALK) {
+                float u[EVAL_ACC_WALK], f[EVAL_ACC_WALK];
+#pragma unroll
+                for (int q = 0; q < EVAL_ACC_WALK; ++q) {
+                    const int k = k1 + q < nk ? k1 + q : nk - 1;
+                    u[q] = sl[k * MST_N_LOSSES + MST_L_U_TOTAL];
+                    f[q] = sl[k * MST_N_LOSSES + leaf];
+                }
+#pragma unroll
+                for (int q = 0; q < EVAL_ACC_WALK; ++q) {
+                    const double next = sum + (count ? 1.0 : (double)f[q]);
+                    // an absent unpitched leaf (NaN total: no percussion) is skipped, not added as 0
+                    sum = k1 + q < nk && (!gated || u[q] == u[q]) ? next : sum;
+                }
+            }
+        }
+        __syncthreads();
+    }
+
+    // ---- the records: clip after clip `channels` pitched ones, the unpitched one, the song-info one
+    const int per = channels + 2;
+    const int m = is_loss ? 0 : w - 2 - MST_N_LOSSES;
+    const int j = m % MST_METRIC_WORDS, which = m / MST_METRIC_WORDS;           // record word; 0 pitched, 1 unpitched, 2 song info
+    const bool plus_one = which == 2 && j == MST_METRIC_WORDS - 1;              // the song-info record's last word counts the clips
+    const int64_t records = (int64_t)n * per;
+    const int recs_per = EVAL_ACC_LDS / MST_METRIC_WORDS;
+    for (int64_t r0 = 0; r0 < records; r0 += recs_per) {
+        const int nr = (int)(records - r0 < recs_per ? records - r0 : recs_per);
+        eval_acc_stage(sm, metrics + r0 * MST_METRIC_WORDS, nr * MST_METRIC_WORDS);
+        __syncthreads();
+        if (owner && !is_loss) {
+            int rr = (int)(r0 % per);                            // the stretch's first record within its clip: the same in every lane
+            for (int r1 = 0; r1 < nr; r1 += EVAL_ACC_WALK) {
+                double v[EVAL_ACC_WALK];
+#pragma unroll
+                for (int q = 0; q < EVAL_ACC_WALK; ++q) v[q] = sm[(r1 + q < nr ? r1 + q : nr - 1) * MST_METRIC_WORDS + j];
+#pragma unroll
+                for (int q = 0; q < EVAL_ACC_WALK; ++q) {
+                    const int kind = rr < channels ? 0 : rr - channels + 1;
+                    const double next = sum + (plus_one ? v[q] + 1.0 : v[q]);
+                    sum = r1 + q < nr && kind == which ? next : sum;
+                    rr = rr + 1 == per ? 0 : rr + 1;
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (owner) acc[w] = sum;
+}
+
+extern "C" int32_t mst_eval_accumulate(const float* losses, const double* metrics, int32_t n_clips, int32_t channels,
+                                       const int32_t* live, double* acc, mst_stream stream) {
+    if (!losses || !metrics || !acc || n_clips < 1 || channels < 1 || ((uintptr_t)metrics & 7) || ((uintptr_t)acc & 7) ||
+        ((uintptr_t)losses & 3) || (int64_t)n_clips * channels >= ((int64_t)1 << 31))
+        return MST_ERR_ARG;
+    hipLaunchKernelGGL(eval_accumulate_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, losses, metrics, (int)n_clips, (int)channels,
+                       live, acc);
+    return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
+}

@@ -47,6 +47,24 @@ DEV_LSTM_TIMEOUT = 1        # mst_amd.h MST_DEV_LSTM_TIMEOUT
 ROLL_NONZERO, ROLL_HARD = 0, 1      # mst_amd.h MST_ROLL_*: record modes of mst_roll_count / mst_roll_compact
 WINDOW_WORDS = 4                    # mst_amd.h mst_window: int32 words per descriptor of mst_clip_window (first, count, src_bars, r0)
 METRIC_WORDS = 8                    # mst_amd.h MST_METRIC_WORDS: doubles per record of mst_roll_metrics / mst_eval_iteration
+ROW_FIELDS = 8                      # mst_amd.h MST_ROW_FIELDS: pieces of a table row one mst_window_inputs call places
+EVAL_ACC_WORDS = 41                 # mst_amd.h MST_EVAL_ACC_WORDS: doubles of a round's running sum (mst_eval_accumulate)
+
+
+class RowFields(C.Structure):
+    """mst_amd.h mst_row_fields: `n` pieces (src, len) of a table row and the workspace offset `dst` each goes to."""
+    _fields_ = [('n', C.c_int32), ('src', C.c_int32 * ROW_FIELDS), ('len', C.c_int32 * ROW_FIELDS), ('dst', C.c_int64 * ROW_FIELDS)]
+
+    @classmethod
+    def of(cls, fields):
+        """From [(src, len, dst)]."""
+        fields = list(fields)
+        if not 1 <= len(fields) <= ROW_FIELDS:
+            raise MstError(f'mst_row_fields holds 1 to {ROW_FIELDS} fields, not {len(fields)}')
+        out = cls(n=len(fields))
+        for f, (src, n, dst) in enumerate(fields):
+            out.src[f], out.len[f], out.dst[f] = int(src), int(n), int(dst)
+        return out
 
 
 def describe_status(word):
@@ -122,6 +140,8 @@ _SIGS = {
     'mst_roll_metrics': (C.c_int32, [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P]),
     'mst_eval_scratch_bytes': (C.c_int64, [_P]),
     'mst_eval_iteration': (C.c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'mst_window_inputs': (C.c_int32, [_P, C.c_int32, C.c_int32, _P, C.c_int32, C.POINTER(RowFields), C.c_int64, _P, _P]),
+    'mst_eval_accumulate': (C.c_int32, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     'mst_plan_step_count': (C.c_int32, [_P, C.c_int32, C.c_int32]),
     'mst_plan_step_info': (C.c_int32, [_P, C.c_int32, C.c_int32, _P]),
     'mst_plan_step_carried': (C.c_int32, [_P, C.c_int32, C.c_int32, _P]),
@@ -241,6 +261,26 @@ class Native:
         addr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()
         check(self.lib.mst_roll_metrics(addr(pred), addr(target), int(n_groups), int(group_cells), int(nfeat), addr(scratch), addr(out),
                                         stream), 'mst_roll_metrics')
+
+    def window_inputs(self, table, table_rows, row_floats, rows, n_clips, fields, clip_stride, ws, stream=None):
+        """mst_window_inputs: for clip k < n_clips and every field (src, len, dst) of `fields` (a RowFields or a list of such
+        triples), ws[dst + k * clip_stride + i] = table[rows[k] * row_floats + src + i], i < len.  `rows` (int32, n_clips) is read
+        on the device; a row outside [0, table_rows) gives quiet NaNs.  `table`, `rows`, `ws` are tensors on one device or raw
+        addresses.  Enqueue-only."""
+        addr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()
+        if not isinstance(fields, RowFields):
+            fields = RowFields.of(fields)
+        check(self.lib.mst_window_inputs(addr(table), int(table_rows), int(row_floats), addr(rows), int(n_clips), C.byref(fields),
+                                         int(clip_stride), addr(ws), stream), 'mst_window_inputs')
+
+    def eval_accumulate(self, losses, metrics, n_clips, channels, live, acc, stream=None):
+        """mst_eval_accumulate: add the first min(max(*live, 0), n_clips) clips of an eval_iteration's `losses` (n_clips x
+        N_LOSSES float32) and `metrics` (n_clips x (channels + 2) x METRIC_WORDS float64) into `acc` (EVAL_ACC_WORDS float64), each
+        word a left-to-right float64 sum.  `live`: one int32 on the device, or None = all clips.  Tensors on one device or raw
+        addresses.  Enqueue-only."""
+        addr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()
+        check(self.lib.mst_eval_accumulate(addr(losses), addr(metrics), int(n_clips), int(channels), addr(live), addr(acc), stream),
+              'mst_eval_accumulate')
 
     def plan(self, dims, device):
         opts = options_from_env()

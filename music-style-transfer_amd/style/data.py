@@ -219,6 +219,12 @@ class WindowBatch:
                 f'songs={self.songs.tolist()}, r0s={self.r0s.tolist()})')
 
 
+class WindowList(list):
+    """What `SongStore.windows` / `SongStore.window_batches` return: a list, with the number of windows the silence rule left
+    out as `.skipped`."""
+    skipped = 0
+
+
 class _RecordPool:
     """The records of many songs back to back on the device: `cells` int32 (capacity,), `feats` float32 (capacity, nfeat)."""
 
@@ -361,6 +367,47 @@ class SongStore:
                         pick.remove(song)
             if len(songs) == K:
                 return WindowBatch(key[0], bars, key[1], key[2], songs, r0s)
+
+    def windows(self, bars, stride=None):
+        """The store's fixed set of windows of `bars` bars, for held-out evaluation: of every song with R >= bars the windows
+        with first bar 0, stride, 2 * stride, ... <= R - bars (stride=None: `bars`, i.e. non-overlapping), as a list of
+        (song id, first bar) — bucket by bucket (sorted keys), within a bucket in ascending song id, within a song in ascending
+        first bar.  A window that fails `window_sounds` is left out; the list's `.skipped` says how many were.  No RNG: the
+        same store gives the same list."""
+        bars, stride = int(bars), int(bars if stride is None else stride)
+        if bars < 1 or stride < 1:
+            raise ValueError('windows: bars and stride must be at least 1')
+        out = WindowList()
+        for key in sorted(self.buckets):
+            for song in sorted(self.buckets[key]['songs']):
+                for r0 in range(0, self.songs[song]['R'] - bars + 1, stride):
+                    if self.window_sounds(song, r0, bars):
+                        out.append((song, r0))
+                    else:
+                        out.skipped += 1
+        return out
+
+    def window_batches(self, bars, K, stride=None):
+        """`windows(bars, stride)` cut into batches of K for a `clips = K` plan: a list of (WindowBatch, live).  Each bucket's
+        windows fill batches of their own (one shape per batch); a bucket's last batch is padded to K by repeating its last
+        window, and `live` is the number of real windows in front.  `.skipped` is `windows`' count."""
+        K = int(K)
+        if K < 1:
+            raise ValueError('window_batches: K must be at least 1')
+        found = self.windows(bars, stride)
+        out = WindowList()
+        out.skipped = found.skipped
+        by_bucket = {}
+        for song, r0 in found:
+            by_bucket.setdefault(self.songs[song]['key'], []).append((song, r0))
+        for key in sorted(by_bucket):
+            group = by_bucket[key]
+            for at in range(0, len(group), K):
+                part = group[at:at + K]
+                live = len(part)
+                part = part + [part[-1]] * (K - live)
+                out.append((WindowBatch(key[0], bars, key[1], key[2], [s for s, _ in part], [r for _, r in part]), live))
+        return out
 
     def describe(self, batch, out):
         """Fill `out` (a host int32 array (2, K, 4)) with the mst_window descriptors of the batch: row 0 for the pitched

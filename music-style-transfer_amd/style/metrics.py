@@ -206,6 +206,25 @@ def append_validation_rows(path, rows):
         out.writerows([row[k] for k in VALIDATION_FIELDS] for row in rows)
 
 
+def round_result(acc):
+    """The 41 doubles mst_eval_accumulate summed over a round (include/mst_amd.h), on the host -> the dict
+    style.train.evaluate returns: `clips` (acc[0]), `losses` (a leaf is its sum / clips; an unpitched leaf its sum / acc[1], the
+    clips with percussion, NaN when there is none — nanmean_leaves' rule), and the three summed records `pitched`, `unpitched`,
+    `song_info` (its last word already counts the clips).  `validation_row` applies to it unchanged."""
+    acc = np.asarray(torch.as_tensor(acc).detach().cpu().numpy(), dtype=np.float64).reshape(-1)
+    if acc.shape != (_native.EVAL_ACC_WORDS,):
+        raise ValueError(f'round_result takes the {_native.EVAL_ACC_WORDS} doubles of mst_eval_accumulate, not {acc.shape}')
+    n, n_unpitched = acc[0], acc[1]
+    sums = acc[2:2 + _native.N_LOSSES]
+    losses = sums / n if n else np.full(_native.N_LOSSES, np.nan)
+    for i, k in enumerate(_native.LOSS_KEYS):
+        if 'unpitched' in k:
+            losses[i] = sums[i] / n_unpitched if n_unpitched else np.nan
+    records = torch.from_numpy(acc[2 + _native.N_LOSSES:].copy()).reshape(3, WORDS)
+    return dict(clips=int(n), losses=losses, pitched=NoteMetrics(records[0]), unpitched=NoteMetrics(records[1]),
+                song_info=SongInfoMetrics(records[2]))
+
+
 def nanmean_leaves(rows):
     """Column means of an (n, 15) array of loss leaves.  The unpitched leaves are NaN for a clip without percussion: they are
     averaged over the clips that have them (NaN when none has).  Any other NaN is a real one and stays."""

@@ -568,6 +568,113 @@ class StyleTransferModel(nn.Module):
         self._publish_grads()
         return st['losses'].clone()
 
+    def eval_windows(self, store, batch, live=None, acc=None):
+        """The forward-only twin of train_windows: the K windows of `batch` (style.data.WindowBatch) of the songs resident in
+        `store` go through the `clips = K` plan of their shape as ONE evaluation pass — forward, get_total_loss(normalize=True)
+        with the inputs as targets and the note metrics, no backward.  One copy from pinned memory carries the 2 K window
+        descriptors, the K table rows of the clips' songs and `live` (9 K + 1 int32); then two mst_clip_window launches crop the
+        windows (one without percussion), mst_window_inputs puts the clips' small inputs from the store's table into their
+        workspace slots, mst_eval_iteration runs the pass and, when `acc` (style._native.EVAL_ACC_WORDS float64 on the model's
+        device) is given, mst_eval_accumulate adds the first `live` clips (default: all K) into it — the rest of a padded batch
+        is not scored.  From the second use of a plan on, that body replays as one hipGraph: descriptors, rows and `live` are
+        read on the device, so a replay serves other songs, other windows and partial batches.  Returns (losses K x 15, metrics
+        K x (C + 2) x 8 float64) of all K clips on the device; nothing is read back.
+
+        It runs on the current stream, behind whatever train_iteration has enqueued on its lanes (their bookkeeping is left
+        alone), in a workspace, note buffers and descriptors of its own per plan: it touches no gradient buffer, no lane, not
+        the lane counter and not train_windows' state, so the training it sits between is the same bits with or without it."""
+        anchor = self._anchor()
+        dev = anchor.device
+        if store.pools[n_pitched_features].cells.device != dev:
+            raise _native.MstError(f'the SongStore lives on {store.device}, the model on {dev}')
+        K, C, R, T, U = batch.K, batch.C, batch.bars, batch.T, batch.percussion
+        live = K if live is None else int(live)
+        if acc is not None and (acc.dtype != torch.float64 or acc.device != dev or not acc.is_contiguous()
+                                or acc.numel() != _native.EVAL_ACC_WORDS):
+            raise _native.MstError(f'eval_windows: acc must be {_native.EVAL_ACC_WORDS} contiguous float64 on {dev}')
+        plan = self._plan(C, R, T, U, dev, clips=K)
+        bucket = store.buckets[(C, T, U)]
+        names = ('mode', 'bpm', 'instr', 'used_instruments', 'bpm_target')
+        st = plan.__dict__.get('_eval_window_state')
+        if st is None:
+            n_desc = 2 * K * _native.WINDOW_WORDS
+            roll = lambda *shape: torch.empty((K,) + shape, dtype=torch.float32, device=dev)
+            fields = []
+            for name, (a, b) in zip(names, bucket['fields']):
+                off, _, numel = plan.slot(name)
+                if numel != b - a:
+                    raise _native.MstError(f'the store keeps {b - a} floats of {name}, the plan reads {numel}')
+                fields.append((a, b - a, off))
+            st = plan.__dict__['_eval_window_state'] = dict(
+                ws=plan.new_ws(), pitched=roll(C, R, T, n_beat_fractions, n_pitched_notes, n_pitched_features),
+                unpitched=roll(1, R, T, n_beat_fractions, n_unpitched_notes, n_unpitched_features) if U else None,
+                losses=torch.empty(K, _native.N_LOSSES, dtype=torch.float32, device=dev),
+                metrics=torch.empty(K, C + 2, _native.METRIC_WORDS, dtype=torch.float64, device=dev),
+                # one int32 buffer: the 2 x K window descriptors, the K table rows, `live`
+                desc=torch.zeros(n_desc + K + 1, dtype=torch.int32, device=dev), n_desc=n_desc,
+                # pinned staging slots of that buffer, each reused only after the copy that last read it (its event)
+                stage=[dict(buf=torch.zeros(n_desc + K + 1, dtype=torch.int32, pin_memory=dev.type == 'cuda'), done=None)
+                       for _ in range(4)],
+                fields=_native.RowFields.of(fields), at=0, graph=None, key=None, uses=0)
+        ws, desc, n_desc = st['ws'], st['desc'], st['n_desc']
+        self.join_lanes_keep()
+        stage = st['stage'][st['at'] % len(st['stage'])]
+        st['at'] += 1
+        if stage['done'] is not None and not stage['done'].query():
+            stage['done'].synchronize()
+        host = stage['buf'].numpy()
+        store.describe(batch, host[:n_desc].reshape(2, K, _native.WINDOW_WORDS))
+        host[n_desc:n_desc + K] = [store.songs[s]['row'] for s in batch.songs.tolist()]
+        host[n_desc + K] = live
+        desc.copy_(stage['buf'], non_blocking=True)
+        if dev.type == 'cuda':
+            stage['done'] = stage['done'] or torch.cuda.Event()
+            stage['done'].record()
+        pools, table = store.pools, bucket['table']
+        win = desc[:n_desc].view(2, K, _native.WINDOW_WORDS)
+        stream = _native.current_stream
+
+        def body():
+            native = _native.get()
+            native.clip_window(pools[n_pitched_features].cells, pools[n_pitched_features].feats, win[0], st['pitched'], K, C, R,
+                               T * n_beat_fractions * n_pitched_notes, n_pitched_features, stream(dev))
+            if U:
+                native.clip_window(pools[n_unpitched_features].cells, pools[n_unpitched_features].feats, win[1], st['unpitched'],
+                                   K, 1, R, T * n_beat_fractions * n_unpitched_notes, n_unpitched_features, stream(dev))
+            # (the table's capacity, not its fill: a capture stays right while songs are added until the table moves)
+            native.window_inputs(table, table.shape[0], table.shape[1], desc[n_desc:n_desc + K], K, st['fields'], plan.clip_stride,
+                                 ws, stream(dev))
+            plan.eval_iteration(self._flat, st['pitched'], st['unpitched'], st['losses'], st['metrics'], ws=ws)
+            if acc is not None:
+                native.eval_accumulate(st['losses'], st['metrics'], K, C, desc[n_desc + K:], acc, stream(dev))
+
+        # keyed by every address the capture bakes in: the parameters, the store's pools and the bucket's table (they move when
+        # they grow) and the accumulator
+        key = (self._flat.data_ptr(), table.data_ptr(), None if acc is None else acc.data_ptr()) + \
+            tuple(t.data_ptr() for p in pools.values() for t in (p.cells, p.feats))
+        g = st['graph'] if st['key'] == key else None
+        if g is None and st['uses'] >= 1 and dev.type == 'cuda' and getattr(self, 'graph_repeated_shapes', True):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                body()
+            st['graph'], st['key'] = g, key
+        st['uses'] += 1
+        if g is not None:
+            plan._touch(ws)
+            g.replay()
+        else:
+            body()
+        return st['losses'].clone(), st['metrics'].clone()
+
+    def eval_accumulator(self):
+        """The model's accumulator of evaluation rounds (style.train.evaluate_windows): EVAL_ACC_WORDS float64 on the model's
+        device, allocated once, so that the graphs of eval_windows bake in one address."""
+        dev = self._anchor().device
+        acc = self.__dict__.get('_eval_acc')
+        if acc is None or acc.device != dev:
+            acc = self.__dict__['_eval_acc'] = torch.zeros(_native.EVAL_ACC_WORDS, dtype=torch.float64, device=dev)
+        return acc
+
     def static_inputs(self, C, R, T, unpitched=True, lane=0):
         """The note-tensor buffers a captured train_iteration of this shape reads (created on first use by train_iteration): a
         loader that writes its H2D copies straight into them saves the per-iteration device copy."""
@@ -605,7 +712,7 @@ class StyleTransferModel(nn.Module):
 
     def __getstate__(self):                          # lane streams / rings / graphs are run-time state, never pickled
         d = dict(self.__dict__)
-        for k in ('_lane_list', '_lane_next'):
+        for k in ('_lane_list', '_lane_next', '_eval_acc'):
             d.pop(k, None)
         return d
 

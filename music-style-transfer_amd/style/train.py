@@ -26,7 +26,8 @@ from style.data import (iter_inputs, instrument_size, n_instruments, included_in
 from style.model import (device, get_total_loss, PitchedChannelsEncoder, UnpitchedChannelsEncoder, PitchedRhythmEncoder,
                          UnpitchedRhythmEncoder, StyleEncoder, MelodyEncoder, SongInfoModel, PitchedStyleApplier,
                          UnpitchedStyleApplier, StyleTransferModel)
-from style.metrics import (NoteMetrics, SongInfoMetrics, append_validation_rows, nanmean_leaves, validation_row, WORDS)
+from style.metrics import (NoteMetrics, SongInfoMetrics, append_validation_rows, nanmean_leaves, round_result, validation_row,
+                           WORDS)
 from style.optim import FusedAdam
 from style.utils.misc import ProgressBar, assert_dir
 from style.utils.parallel import iter_parallel, ParallelIterable
@@ -222,10 +223,27 @@ def evaluate(model, inputs, n_clips, sparse_input=False):
                 unpitched=NoteMetrics(records[:, 1]).sum(), song_info=SongInfoMetrics.from_device(records[:, 2]).sum())
 
 
+def evaluate_windows(model, store, bars, K, stride=None):
+    """One held-out round over the store's fixed set of windows (style.data.SongStore.window_batches(bars, K, stride)): every
+    batch, across shape buckets, goes through StyleTransferModel.eval_windows into ONE accumulator the model owns (zeroed
+    here; records add, and the pitched record is already summed over the channels, so buckets of different C share it) — per
+    batch one small upload and one graph replay, at the end ONE copy of 41 doubles to the host.  The padding of a bucket's
+    last batch is not scored.  Every round scores the same windows, so rounds are comparable.  Returns `evaluate`'s dict
+    (style.metrics.round_result: clips = the windows counted) plus `windows_skipped`, the windows the silence rule left out."""
+    batches = store.window_batches(bars, K, stride)
+    acc = model.eval_accumulator()
+    acc.zero_()
+    for batch, live in batches:
+        model.eval_windows(store, batch, live=live, acc=acc)
+    result = round_result(acc.cpu())                  # the one D2H copy
+    result['windows_skipped'] = batches.skipped
+    return result
+
+
 def train(model, inputs, n_iterations=5000, iter_size=2, training_info_path='training.csv', save_path='snapshots/',
           save_interval=100, flush_every=20, progress=True, optimizer=None, fused=True, sparse_input=False,
           max_grad_norm=None, skip_nonfinite=False, save_optimizer=False, eval_inputs=None, eval_every=0, eval_clips=8,
-          eval_info_path='validation.csv', batch_clips=None, window_bars=16, store_songs=64, window_seed=0):
+          eval_info_path='validation.csv', batch_clips=None, window_bars=16, store_songs=64, window_seed=0, eval_windows=None):
     """`inputs`: iterator of (filename, get_input(...)) tuples, e.g. iter_parallel(iter_inputs(...)).
     fused=True runs a loop body as ONE C-ABI call (StyleTransferModel.train_iteration: same arithmetic, same gradients, no
     autograd graph); fused=False is the reference's own sequence model(...) -> get_total_loss -> backward.
@@ -251,9 +269,16 @@ def train(model, inputs, n_iterations=5000, iter_size=2, training_info_path='tra
     StyleTransferModel.train_windows (one batched pass over the K windows, cropped on the device) and optimizer.step().  One
     CSV row per iteration holds the loss leaves averaged over the K clips (on the device).  `iter_size` is ignored with a
     warning: K takes its place.  Needs fused=True; sparse_input only decides how evaluation rounds upload their songs.
-    batch_clips=None leaves the loop exactly as it is."""
+    batch_clips=None leaves the loop exactly as it is.
+    eval_windows = M (with batch_clips and eval_inputs; ValueError otherwise) makes validation follow: before the loop the next M
+    usable songs of `eval_inputs` go into a second SongStore, and every due round is `evaluate_windows` over that store's fixed
+    windows of `window_bars` bars in batches of `batch_clips` — the same windows every round, summed on the device.  `eval_clips`
+    is not used then; the CSV's `clips` column is the number of windows counted.  eval_windows=None: every path is as above."""
     if optimizer is not None and (max_grad_norm is not None or skip_nonfinite):
         raise ValueError('max_grad_norm / skip_nonfinite configure the default optimizer; with optimizer= set them on that optimizer')
+    if eval_windows is not None and (batch_clips is None or eval_inputs is None or int(eval_windows) < 1):
+        raise ValueError('eval_windows = M >= 1 needs batch_clips (the shape and batch size of the windows) and eval_inputs (the '
+                         'held-out songs)')
     windows = None
     if batch_clips is not None:
         if not fused:
@@ -265,6 +290,11 @@ def train(model, inputs, n_iterations=5000, iter_size=2, training_info_path='tra
         windows = (fill_store(inputs, int(store_songs)), np.random.default_rng(window_seed), int(batch_clips), int(window_bars))
         if not len(windows[0]):
             raise ValueError('batch_clips: `inputs` held no usable song')
+    eval_store = None
+    if eval_windows is not None:
+        eval_store = fill_store(eval_inputs, int(eval_windows))
+        if not len(eval_store):
+            raise ValueError('eval_windows: `eval_inputs` held no usable song')
     feeder = None
     if sparse_input and windows is None:
         feeder = ParallelIterable(iter_sparse(inputs))
@@ -272,7 +302,8 @@ def train(model, inputs, n_iterations=5000, iter_size=2, training_info_path='tra
     try:
         return _train_loop(model, inputs, n_iterations, iter_size, training_info_path, save_path, save_interval, flush_every,
                            progress, optimizer, fused, sparse_input, max_grad_norm, skip_nonfinite, save_optimizer,
-                           eval_inputs if eval_every and eval_every > 0 else None, eval_every, eval_clips, eval_info_path, windows)
+                           eval_inputs if eval_every and eval_every > 0 else None, eval_every, eval_clips, eval_info_path, windows,
+                           eval_store)
     finally:
         if feeder is not None:
             feeder.stop(timeout=5.)
@@ -280,7 +311,7 @@ def train(model, inputs, n_iterations=5000, iter_size=2, training_info_path='tra
 
 def _train_loop(model, inputs, n_iterations, iter_size, training_info_path, save_path, save_interval, flush_every, progress,
                 optimizer, fused, sparse_input, max_grad_norm=None, skip_nonfinite=False, save_optimizer=False,
-                eval_inputs=None, eval_every=0, eval_clips=8, eval_info_path='validation.csv', windows=None):
+                eval_inputs=None, eval_every=0, eval_clips=8, eval_info_path='validation.csv', windows=None, eval_store=None):
     optimizer = optimizer or FusedAdam(model, lr=.01, step_size=200, gamma=.9, max_grad_norm=max_grad_norm,
                                        skip_nonfinite=skip_nonfinite)
     optimizer.zero_grad()
@@ -298,7 +329,8 @@ def _train_loop(model, inputs, n_iterations, iter_size, training_info_path, save
             log.add(iteration, packed)
             optimizer.step()                      # K clips have accumulated: K takes iter_size's place
             _after_iteration(model, optimizer, log, pbar, iteration, eval_inputs, eval_every, eval_clips, eval_info_path,
-                             sparse_input, save_interval, save_path, save_optimizer)
+                             sparse_input, save_interval, save_path, save_optimizer,
+                             None if eval_store is None else (eval_store, window_bars, batch_clips))
             continue
         if sparse_input:
             input = next(inputs)
@@ -336,10 +368,14 @@ def _train_loop(model, inputs, n_iterations, iter_size, training_info_path, save
 
 
 def _after_iteration(model, optimizer, log, pbar, iteration, eval_inputs, eval_every, eval_clips, eval_info_path, sparse_input,
-                     save_interval, save_path, save_optimizer):
-    """What follows the optimizer step of an iteration: the evaluation round and the snapshot that are due."""
+                     save_interval, save_path, save_optimizer, eval_windowed=None):
+    """What follows the optimizer step of an iteration: the evaluation round and the snapshot that are due.  `eval_windowed`:
+    (store, bars, K) of a windowed round (evaluate_windows) in place of `evaluate`."""
     if eval_inputs is not None and (iteration + 1) % eval_every == 0:
-        result = evaluate(model, eval_inputs, eval_clips, sparse_input=sparse_input)
+        if eval_windowed is not None:
+            result = evaluate_windows(model, *eval_windowed)
+        else:
+            result = evaluate(model, eval_inputs, eval_clips, sparse_input=sparse_input)
         if eval_info_path:
             append_validation_rows(eval_info_path, [validation_row(iteration, result['clips'], result['losses'], result['pitched'],
                                                                    result['unpitched'], result['song_info'])])

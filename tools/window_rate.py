@@ -8,8 +8,13 @@ and their spread).
                bars, in iterations (= clips) per second;
   --kernels    also times, under device events, the two mst_clip_window launches that crop 64 clips against mst_clip_scatter
                writing the same destinations from per-clip record buffers (both are bound by the same stores).
+  --eval       times held-out evaluation instead of training: style.train.evaluate_windows rounds over the store's fixed
+               windows (windows per second, for every K of --clips; --eval-stride sets the windows' stride), beside it
+               style.train.evaluate on the same songs, one song per call (songs per second), and, under device events, the
+               two launches a windowed round adds: mst_window_inputs and mst_eval_accumulate at 64 clips.
 One JSON line per measurement; --out writes them all to a file.
-Usage on the GPU box: python tools/window_rate.py [--songs 16] [--iters 150] [--runs 5] [--one-clip] [--kernels] [--out FILE]"""
+Usage on the GPU box: python tools/window_rate.py [--songs 16] [--iters 150] [--runs 5] [--one-clip] [--kernels] [--eval
+                      [--eval-stride S]] [--out FILE]"""
 import argparse
 import json
 import os
@@ -141,6 +146,78 @@ def kernels(store, K, reps=50):
     return res
 
 
+def eval_rounds(model, store, K, stride, runs, rounds=3):
+    """Windows per second of evaluate_windows rounds (host clock around `rounds` rounds; each ends in its one download)."""
+    from style.train import evaluate_windows
+    for _ in range(2):                                    # eager, then capture + replay (per plan)
+        res = evaluate_windows(model, store, BARS, K, stride)
+    torch.cuda.synchronize()
+    n_batches = len(store.window_batches(BARS, K, stride))
+    rates, ms = [], []
+    for _ in range(runs):
+        t0 = time.perf_counter()
+        for _ in range(rounds):
+            res = evaluate_windows(model, store, BARS, K, stride)
+        dt = time.perf_counter() - t0
+        rates.append(rounds * res['clips'] / dt)
+        ms.append(dt / rounds * 1e3)
+    model.check_device_status()
+    return dict(what='evaluate_windows', K=K, bars=BARS, C=C, T=T, stride=stride or BARS, windows=res['clips'], batches=n_batches,
+                windows_skipped=res['windows_skipped'], round_ms=spread(ms), unit='windows/s', **spread(rates))
+
+
+def eval_per_song(model, songs, runs):
+    """Songs per second of style.train.evaluate, one whole song per eval_iteration call, on the same songs."""
+    from style.train import evaluate
+    run = lambda: evaluate(model, iter(songs), len(songs), sparse_input=True)
+    run()                                                 # builds the plan of every shape
+    torch.cuda.synchronize()
+    rates = []
+    for _ in range(runs):
+        t0 = time.perf_counter()
+        res = run()
+        rates.append(res['clips'] / (time.perf_counter() - t0))
+    bars = sum(p.shape[1] for _, (_, p, _, _, _) in songs)
+    return dict(what='evaluate(sparse_input=True), one song per call', songs=len(songs), bars=bars, C=C, T=T, unit='songs/s',
+                **spread(rates))
+
+
+def eval_kernels(model, store, K, reps=50):
+    """Microseconds, under device events, of mst_window_inputs placing K clips' small inputs and of mst_eval_accumulate folding K
+    clips."""
+    from style import _native
+    native, dev = _native.get(), store.device
+    plan = model._plan(C, BARS, T, True, dev, clips=K)
+    bucket = store.buckets[(C, T, True)]
+    table = bucket['table']
+    names = ('mode', 'bpm', 'instr', 'used_instruments', 'bpm_target')
+    fields = _native.RowFields.of([(a, b - a, plan.slot(n)[0]) for n, (a, b) in zip(names, bucket['fields'])])
+    ws = plan.new_ws()
+    rows = torch.tensor([k % len(bucket['songs']) for k in range(K)], dtype=torch.int32, device=dev)
+    losses = torch.rand(K, _native.N_LOSSES, device=dev)
+    metrics = torch.rand(K, C + 2, _native.METRIC_WORDS, dtype=torch.float64, device=dev)
+    live = torch.tensor([K], dtype=torch.int32, device=dev)
+    acc = torch.zeros(_native.EVAL_ACC_WORDS, dtype=torch.float64, device=dev)
+    stream = _native.current_stream(dev)
+    calls = (('mst_window_inputs', lambda: native.window_inputs(table, table.shape[0], table.shape[1], rows, K, fields,
+                                                                 plan.clip_stride, ws, stream)),
+             ('mst_eval_accumulate', lambda: native.eval_accumulate(losses, metrics, K, C, live, acc, stream)))
+    res = []
+    for name, fn in calls + calls:                         # alternated
+        fn()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            times.append(a.elapsed_time(b) * 1e3)
+        res.append(dict(what=name, K=K, C=C, unit='us', **spread(times)))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--songs', type=int, default=16)
@@ -149,6 +226,8 @@ def main():
     ap.add_argument('--clips', type=int, nargs='*', default=[8, 64])
     ap.add_argument('--one-clip', action='store_true')
     ap.add_argument('--kernels', action='store_true')
+    ap.add_argument('--eval', action='store_true')
+    ap.add_argument('--eval-stride', type=int, default=None)
     ap.add_argument('--out')
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -161,9 +240,14 @@ def main():
     if args.kernels:
         results += kernels(store, 64)
     model = build_model(seed=108)
+    if args.eval:
+        for K in args.clips:
+            results.append(eval_rounds(model, store, K, args.eval_stride, args.runs))
+        results.append(eval_per_song(model, songs, args.runs))
+        results += eval_kernels(model, store, 64)
     opt = FusedAdam(model)
     opt.zero_grad()
-    for K in args.clips:
+    for K in [] if args.eval else args.clips:
         results.append(windowed(model, opt, store, K, args.iters, args.runs))
     if args.one_clip:
         results.append(one_clip(build_model(seed=108), songs, args.iters * 16, args.runs))

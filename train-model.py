@@ -2,12 +2,14 @@
 """Drop-in for the reference's train-model.py on the MI355X path: same constants, same loop semantics
 (music-style-transfer_amd/style/train.py), run from the repository root:
 
-    python train-model.py [--batch-clips K [--window-bars R] [--store-songs N] [--window-seed S]] [data_path] [n_eval_files [eval_every]]
+    python train-model.py [--batch-clips K [--window-bars R] [--store-songs N] [--window-seed S] [--eval-windows M]] [data_path] [n_eval_files [eval_every]]
 
 With n_eval_files > 0 the last that many of the sorted files are held out of training and evaluated (forward, loss and note
 metrics, no backward) after every eval_every-th iteration (default 100) into validation.csv.
 With --batch-clips K the loop trains on windowed batches (style.train.train's batch_clips, window_bars, store_songs,
 window_seed): N songs are kept on the device and every iteration is one batched pass over K windows of R bars of them.
+With --eval-windows M as well (and n_eval_files > 0) validation follows: M held-out songs are kept on the device and every
+evaluation round scores the same fixed windows of R bars of them in batches of K (style.train.evaluate_windows).
 """
 import os
 import sys
@@ -18,7 +20,7 @@ sys.path.insert(0, os.path.join(ROOT, 'music-style-transfer_amd'))
 from style.train import main  # noqa: E402
 
 WINDOW_OPTIONS = {'--batch-clips': 'batch_clips', '--window-bars': 'window_bars', '--store-songs': 'store_songs',
-                  '--window-seed': 'window_seed'}
+                  '--window-seed': 'window_seed', '--eval-windows': 'eval_windows'}
 
 
 def split_options(argv):
@@ -34,7 +36,7 @@ def split_options(argv):
         else:
             positional.append(arg)
     if options and 'batch_clips' not in options:
-        raise SystemExit('--window-bars, --store-songs and --window-seed go with --batch-clips')
+        raise SystemExit('--window-bars, --store-songs, --window-seed and --eval-windows go with --batch-clips')
     return positional, options
 
 
