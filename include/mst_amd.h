@@ -466,6 +466,17 @@ int32_t mst_audio_style_iteration(const mst_audio_plan* p, float* x, const float
 /* test hook of the plan builder's single-launch weight-gradient reduction guard: do two column blocks of one row-major matrix
  * (row pitch ld), given by their first elements' offsets from the matrix's element (0, 0), share no element?  1 = disjoint. */
 int32_t mst_debug_slab_columns_disjoint(int64_t off_x, int32_t width_x, int64_t off_y, int32_t width_y, int32_t ld);
+/* test hook of the 32x32 GEMM kernel's tile loaders: walks a whole operand on the host with the per-lane walk state the kernel
+ * uses (every lane of every 32-row tile, k-tiles of depth kd = 32 | 64 | 128 over [k0, k1), k0 a multiple of 8, k1 <= K) and
+ * compares each element's predicates and offset with the closed-form accessor.  kind: 3 im2col (as A: lanes walk k, `rows` = M;
+ * as_b = 1: lanes walk the column, `rows` = N), 4 permuted weight (as_b = 1; (pb, pc) = (14, 5) or (47, 2), row pitch ld),
+ * 5 conv gradient (as A, oc out channels).  Returns the number of mismatching elements (0 = the walk is the accessor), or a
+ * negative MST_ERR_*; *compared (nullable) receives the number of elements walked. */
+int64_t mst_debug_gemm_walk(int32_t kind, int32_t as_b, int32_t rows, int32_t K, int32_t k0, int32_t k1, int32_t kd, int32_t ld,
+                            int32_t pb, int32_t pc, int32_t oc, int64_t* compared);
+/* the members of GEMM launch step `step` (as mst_plan_step_gemms, same order), 2 values each: {kernel variant (GV_* of the
+ * plan's tiling), k-tile depth (32 | 64 | 128 on the 32x32 tiling, 32 on the 64x64 tiling)}.  Returns the member count (<= cap). */
+int32_t mst_plan_step_gemm_kinds(const mst_plan* p, int32_t stage_mask, int32_t backward, int32_t step, int32_t* out, int32_t cap);
 
 const char* mst_version(void);
 

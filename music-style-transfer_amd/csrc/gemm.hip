@@ -52,7 +52,7 @@ typedef const MST_GLOBAL_AS float* gcptr;
 // Element offset of operand(i, j) — branch-free; `ok` is cleared for im2col padding taps.
 // (i, j) = (m, k) for the A operand and (k, n) for the B operand.
 template <int KIND>
-__device__ __forceinline__ int off_of(const Operand& o, int i, int j, bool& ok) {
+__host__ __device__ __forceinline__ int off_of(const Operand& o, int i, int j, bool& ok) {
     if constexpr (KIND == OPK_DENSE) {
         return i * (int)o.si + j * (int)o.sj;
     } else if constexpr (KIND == OPK_ACTGRAD) {      // value(row, col): transposed => i is the column
@@ -89,6 +89,175 @@ __device__ __forceinline__ int off_of(const Operand& o, int i, int j, bool& ok) 
     }
 }
 
+// ---- per-lane walk state of gemm_body's tile loaders ----------------------------------------------
+// A lane of the 1024-lane workgroup loads NL = KD / 32 elements of each operand's 32 x KD tile: element i sits at
+// (row, k) = (tid / KD + (1024 / KD) i, tid % KD) when lanes walk k (KF = 1), (tid % 32, tid / 32 + 32 i) when they walk the
+// row index (KF = 0).  So either the lane's k position inside the tile or its row never changes from k-tile to k-tile, and
+// the divisions of the im2col / permuted-weight accessors (off_of re-derived them per element and k-tile: 30-34 integer
+// multiplies and ~230 VALU instructions per wave and k-tile at KD = 128, against 52 for a dense pair) are done ONCE, in
+// init(); advance() moves the state one k-tile on with adds and compares of constants, at() gives element i's offset and
+// predicates.  Same offsets, same predicates as off_of: mst_debug_gemm_walk runs these very functions on the host against it.
+// inb: element inside the matrix and the k range; ok: inb and not an im2col padding tap.
+template <int KF, int KD> __host__ __device__ __forceinline__ int walk_row(int tid, int i) { return KF ? tid / KD + (GEMM_THREADS / KD) * i : (tid & 31); }
+template <int KF, int KD> __host__ __device__ __forceinline__ int walk_kl(int tid, int i) { return KF ? tid % KD : (tid >> 5) + (GEMM_THREADS / 32) * i; }
+// the permuted weights the model has: PERM 1 = the conv's (pb, pc) = (14, 5), PERM 2 = the unpitched Linear's (47, 2)
+template <int PERM> struct PermOf { static constexpr int PB = PERM == 1 ? CONV_K : NUN, PC = PERM == 1 ? NPF : NUF; };
+__host__ __device__ __forceinline__ int perm_case(int pb, int pc) { return (pb == CONV_K && pc == NPF) ? 1 : ((pb == NUN && pc == NUF) ? 2 : 0); }
+
+// every other operand: no state, off_of as it is (dense / activation-gradient offsets are affine and strength-reduce by themselves)
+template <int KIND, bool ISB, int KF, int KD, int PERM>
+struct OpWalk {
+    int tid, r0, R;
+    __host__ __device__ __forceinline__ void init(const Operand&, int tid_, int r0_, int R_, int) { tid = tid_; r0 = r0_; R = R_; }
+    __host__ __device__ __forceinline__ void advance() {}
+    __host__ __device__ __forceinline__ int at(const Operand& o, int i, int kt, int k1, bool& inb, bool& ok) const {
+        const int r = r0 + walk_row<KF, KD>(tid, i), k = kt + walk_kl<KF, KD>(tid, i);
+        inb = (r < R) & (k < k1);
+        ok = inb;
+        return ISB ? off_of<KIND>(o, k, r, ok) : off_of<KIND>(o, r, k, ok);
+    }
+};
+// im2col as A, lanes walk k (the conv's forward): k = (f, rem) is split once; a k-tile adds KD % 70 to rem with one carry into f.
+// Rows step by a multiple of 8, so the octave (and with it the padding predicate's row part e0) is the same for all i.
+template <int KD, int PERM>
+struct OpWalk<OPK_IM2COL, false, 1, KD, PERM> {
+    static constexpr int BC = CONV_K * NPF, ROWS = GEMM_THREADS / KD;
+    static_assert(ROWS % NOCT == 0, "a lane's rows share their octave");
+    int m0, R, kl, rem, e0, off0;
+    __host__ __device__ __forceinline__ void init(const Operand&, int tid, int r0, int R_, int k0) {
+        m0 = r0 + tid / KD; R = R_; kl = tid % KD;
+        const int j = k0 + kl, f = j / BC;
+        rem = j - f * BC;
+        e0 = (NDEG * (m0 & 7) - CONV_PAD) * NPF;
+        off0 = (m0 >> 3) * (NF * NPN * NPF) + f * (NPN * NPF) + e0 + rem;
+    }
+    __host__ __device__ __forceinline__ void advance() {
+        rem += KD % BC; off0 += (KD / BC) * (NPN * NPF) + KD % BC;
+        if (rem >= BC) { rem -= BC; off0 += NPN * NPF - BC; }
+    }
+    __host__ __device__ __forceinline__ int at(const Operand&, int i, int kt, int k1, bool& inb, bool& ok) const {
+        const int e = e0 + rem;
+        inb = (m0 + ROWS * i < R) & (kt + kl < k1);
+        ok = inb & (e >= 0) & (e < NPN * NPF);
+        return off0 + i * (ROWS / NOCT) * (NF * NPN * NPF);
+    }
+};
+// im2col as B, lanes walk the column (the conv's weight gradient): the column's (f, rem) and, k-tiles being multiples of 8 rows,
+// the row's octave never change: the padding predicate is a lane constant and a k-tile adds KD / 8 positions
+template <int KD, int PERM>
+struct OpWalk<OPK_IM2COL, true, 0, KD, PERM> {
+    static constexpr int BC = CONV_K * NPF;
+    static_assert(KD % NOCT == 0, "a k-tile is whole positions");
+    int kl, off0; bool colok, padok;
+    __host__ __device__ __forceinline__ void init(const Operand&, int tid, int r0, int R, int k0) {
+        const int n = r0 + (tid & 31), f = n / BC, rem = n - f * BC;
+        kl = tid >> 5;
+        const int k = k0 + kl, e = (NDEG * (k & 7) - CONV_PAD) * NPF + rem;
+        colok = n < R;
+        padok = (e >= 0) & (e < NPN * NPF);
+        off0 = (k >> 3) * (NF * NPN * NPF) + f * (NPN * NPF) + e;
+    }
+    __host__ __device__ __forceinline__ void advance() { off0 += (KD / NOCT) * (NF * NPN * NPF); }
+    __host__ __device__ __forceinline__ int at(const Operand&, int i, int kt, int k1, bool& inb, bool& ok) const {
+        inb = colok & (kt + kl + (GEMM_THREADS / 32) * i < k1);
+        ok = inb & padok;
+        return off0 + i * (GEMM_THREADS / 32 / NOCT) * (NF * NPN * NPF);
+    }
+};
+// permuted weight as B, lanes walk k: k = (a, bb, c) in mixed radix (., PB, PC) is split once and carried; a k-tile adds the
+// digits of KD with two carries.  off0 follows the digits: column a * BC + c * PB + bb of row n0.
+template <int KD, int PERM>
+struct OpWalk<OPK_PERMW, true, 1, KD, PERM> {
+    static constexpr int PB = PermOf<PERM>::PB, PC = PermOf<PERM>::PC, BC = PB * PC, ROWS = GEMM_THREADS / KD;
+    static constexpr int DA = KD / BC, DB = KD % BC / PC, DC = KD % BC % PC;
+    static_assert(PERM == 1 || PERM == 2, "one of the model's two permutations");
+    int n0, R, kl, c, bb, off0, rstep;
+    __host__ __device__ __forceinline__ void init(const Operand& o, int tid, int r0, int R_, int k0) {
+        n0 = r0 + tid / KD; R = R_; kl = tid % KD;
+        const int j = k0 + kl, a = j / BC, rem = j - a * BC;
+        bb = rem / PC; c = rem - bb * PC;
+        off0 = n0 * o.ld + a * BC + c * PB + bb;
+        rstep = ROWS * o.ld;
+    }
+    __host__ __device__ __forceinline__ void advance() {
+        c += DC; bb += DB; off0 += DA * BC + DC * PB + DB;
+        if (c >= PC) { c -= PC; bb += 1; off0 += 1 - BC; }          // c * PB gives up PC * PB = BC, bb takes the carry
+        if (bb >= PB) { bb -= PB; off0 += BC - PB; }                // bb gives up PB, a takes the carry
+    }
+    __host__ __device__ __forceinline__ int at(const Operand&, int i, int kt, int k1, bool& inb, bool& ok) const {
+        inb = (n0 + ROWS * i < R) & (kt + kl < k1);
+        ok = inb;
+        return off0 + i * rstep;
+    }
+};
+// conv gradient as A, lanes walk k (the conv's weight gradient): no divisions; the k part is carried like the others'
+template <int KD, int PERM>
+struct OpWalk<OPK_CONVGRAD, false, 1, KD, PERM> {
+    static constexpr int ROWS = GEMM_THREADS / KD;
+    static_assert(KD % NOCT == 0, "a k-tile is whole positions");
+    int m0, R, kl, off0, kstep;
+    __host__ __device__ __forceinline__ void init(const Operand& o, int tid, int r0, int R_, int k0) {
+        m0 = r0 + tid / KD; R = R_; kl = tid % KD;
+        const int j = k0 + kl;
+        off0 = (j >> 3) * (o.oc * NOCT) + m0 * NOCT + (j & 7);
+        kstep = (KD / NOCT) * (o.oc * NOCT);
+    }
+    __host__ __device__ __forceinline__ void advance() { off0 += kstep; }
+    __host__ __device__ __forceinline__ int at(const Operand&, int i, int kt, int k1, bool& inb, bool& ok) const {
+        inb = (m0 + ROWS * i < R) & (kt + kl < k1);
+        ok = inb;
+        return off0 + i * ROWS * NOCT;
+    }
+};
+
+// Host-side check of a walker against off_of: every lane of every tile of an operand with `rows` rows (M, or N for a B
+// operand) walks the k range [k0, k1) exactly as gemm_body does; counts the elements whose (ok, offset where ok) differ.
+template <int KIND, bool ISB, int KF, int KD, int PERM>
+static int64_t walk_mismatches(const Operand& o, int rows, int k0, int k1, int64_t* compared) {
+    constexpr int NL = GEMM_BM * KD / GEMM_THREADS;
+    int64_t bad = 0, seen = 0;
+    for (int r0 = 0; r0 < rows; r0 += GEMM_BM)
+        for (int tid = 0; tid < GEMM_THREADS; ++tid) {
+            OpWalk<KIND, ISB, KF, KD, PERM> w;
+            w.init(o, tid, r0, rows, k0);
+            for (int kt = k0; kt < k1; kt += KD) {
+                for (int i = 0; i < NL; ++i) {
+                    bool inb, ok;
+                    const int off = w.at(o, i, kt, k1, inb, ok);
+                    const int r = r0 + walk_row<KF, KD>(tid, i), k = kt + walk_kl<KF, KD>(tid, i);
+                    const bool rinb = (r < rows) & (k < k1);
+                    bool rok = rinb;
+                    const int roff = ISB ? off_of<KIND>(o, k, r, rok) : off_of<KIND>(o, r, k, rok);
+                    // what the loader uses: the predicates, the offset of an element that is loaded (the bias-ones column of
+                    // an im2col B operand is inb without being loaded; its offset is compared all the same)
+                    bad += (inb != rinb) | (ok != rok) | (rinb & (off != roff));
+                    ++seen;
+                }
+                w.advance();
+            }
+        }
+    if (compared) *compared = seen;
+    return bad;
+}
+
+extern "C" int64_t mst_debug_gemm_walk(int32_t kind, int32_t as_b, int32_t rows, int32_t K, int32_t k0, int32_t k1, int32_t kd,
+                                       int32_t ld, int32_t pb, int32_t pc, int32_t oc, int64_t* compared) {
+    if (rows < 1 || K < 1 || k0 < 0 || k0 % 8 || k1 > K || k0 > k1 || (kd != 32 && kd != 64 && kd != 128)) return MST_ERR_ARG;
+    Operand o{};
+    o.kind = kind; o.ld = ld; o.pb = pb; o.pc = pc; o.oc = oc; o.ones_at = -1;
+#define WALK_KD(KIND, ISB, KF, PERM)                                                                      \
+    return kd == 32 ? walk_mismatches<KIND, ISB, KF, 32, PERM>(o, rows, k0, k1, compared)                 \
+                    : (kd == 64 ? walk_mismatches<KIND, ISB, KF, 64, PERM>(o, rows, k0, k1, compared)     \
+                                : walk_mismatches<KIND, ISB, KF, 128, PERM>(o, rows, k0, k1, compared));
+    if (kind == OPK_IM2COL && !as_b) { WALK_KD(OPK_IM2COL, false, 1, 0) }
+    if (kind == OPK_IM2COL && as_b) { WALK_KD(OPK_IM2COL, true, 0, 0) }
+    if (kind == OPK_CONVGRAD && !as_b) { WALK_KD(OPK_CONVGRAD, false, 1, 0) }
+    if (kind == OPK_PERMW && as_b && perm_case(pb, pc) == 1) { WALK_KD(OPK_PERMW, true, 1, 1) }
+    if (kind == OPK_PERMW && as_b && perm_case(pb, pc) == 2) { WALK_KD(OPK_PERMW, true, 1, 2) }
+#undef WALK_KD
+    return MST_ERR_UNSUPPORTED;
+}
+
 template <int OK>
 __device__ __forceinline__ void store_out(const GemmDesc& d, float* cbase, const float* bias, int m, int n, int split, float acc) {
     const OutSpec& o = d.out;
@@ -119,7 +288,7 @@ __device__ __forceinline__ void store_out(const GemmDesc& d, float* cbase, const
     }
 }
 
-template <int AK, int BKIND, int OK, int AKF, int BKF, int KD>
+template <int AK, int BKIND, int OK, int AKF, int BKF, int KD, int PERM = 0>
 __device__ __forceinline__ void gemm_body(const GemmDesc& d, const Bases& b, const int tile, const int split,
                                           float (*As)[GEMM_BM + GEMM_PAD], float (*Bs)[GEMM_BN + GEMM_PAD]) {
     // 32x32 output tile per workgroup, 128-deep k-tile: wave w owns k rows [32w, 32w+32) of the
@@ -152,38 +321,44 @@ __device__ __forceinline__ void gemm_body(const GemmDesc& d, const Bases& b, con
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 
     constexpr int NT = GEMM_THREADS, NW = NT / 64;
-    constexpr int NL = GEMM_BM * KD / NT;            // tile elements per lane and operand (2 / 4 / 8)
+    constexpr int NL = GEMM_BM * KD / NT;            // tile elements per lane and operand (1 / 2 / 4)
     constexpr int KW = KD / NW;                      // k rows of the tile each wave reduces
     float va[NL], ya[NL], vb[NL];
 
-    // element e = tid + NT*i of the 32 x KD tile: (row, k) = (e / KD, e % KD) when lanes walk k,
-    // (e % 32, e / 32) when lanes walk the row index
-#define A_ROW(i) (AKF ? (tid / KD) + (NT / KD) * (i) : (tid & 31))
-#define A_KL(i) (AKF ? (tid % KD) : (tid >> 5) + (NT / 32) * (i))
-#define B_ROW(i) (BKF ? (tid / KD) + (NT / KD) * (i) : (tid & 31))
-#define B_KL(i) (BKF ? (tid % KD) : (tid >> 5) + (NT / 32) * (i))
+    // element i of the lane: (row, k) = walk_row / walk_kl.  The operands' offsets and predicates come from per-lane walk
+    // state (OpWalk): set up here, moved on by one k-tile behind every issue
+#define A_ROW(i) walk_row<AKF, KD>(tid, i)
+#define A_KL(i) walk_kl<AKF, KD>(tid, i)
+#define B_ROW(i) walk_row<BKF, KD>(tid, i)
+#define B_KL(i) walk_kl<BKF, KD>(tid, i)
+    OpWalk<AK, false, AKF, KD, PERM> wa;
+    OpWalk<BKIND, true, BKF, KD, PERM> wb;
+    wa.init(d.A, tid, tm * GEMM_BM, M, k0);
+    wb.init(d.B, tid, tn * GEMM_BN, N, k0);
 #define GEMM_ISSUE(KT)                                                                                     \
     {                                                                                                      \
         _Pragma("unroll") for (int i = 0; i < NL; ++i) {                                                   \
-            const int m = tm * GEMM_BM + A_ROW(i), ka = (KT) + A_KL(i);                                    \
-            bool oka = (m < M) & (ka < k1);                                                                \
-            int ia = off_of<AK>(d.A, m, ka, oka);                                                          \
+            bool ina, oka;                                                                                 \
+            int ia = wa.at(d.A, i, (KT), k1, ina, oka);                                                    \
             ia = oka ? ia : 0;                                                                             \
             const float x = baseA[(unsigned)ia];                                                           \
             if constexpr (AK == OPK_ACTGRAD || AK == OPK_CONVGRAD) {                                       \
                 const float y = baseA2[(unsigned)ia];                                                      \
-                const int col = (AK == OPK_ACTGRAD) ? (a_tr ? m : ka) : 0;                                 \
+                int col = 0;                                                                               \
+                if constexpr (AK == OPK_ACTGRAD) col = a_tr ? tm * GEMM_BM + A_ROW(i) : (KT) + A_KL(i);    \
                 ya[i] = act_bwd(a_act, y, col);                                                            \
             } else ya[i] = 1.f;                                                                            \
             va[i] = oka ? x : 0.f;                                                                         \
-            const int n = tn * GEMM_BN + B_ROW(i), kb = (KT) + B_KL(i);                                    \
-            bool okb = (n < N) & (kb < k1);                                                                \
-            const bool one = okb & (n == b_ones);                                                          \
-            int ib = off_of<BKIND>(d.B, kb, n, okb);                                                       \
+            bool inb, okb;                                                                                 \
+            int ib = wb.at(d.B, i, (KT), k1, inb, okb);                                                    \
+            bool one = false;                                                                              \
+            if constexpr (BKIND == OPK_DENSE || BKIND == OPK_IM2COL) one = inb & (tn * GEMM_BN + B_ROW(i) == b_ones); \
             ib = (okb & !one) ? ib : 0;                                                                    \
             const float w = baseB[(unsigned)ib];                                                           \
             vb[i] = one ? 1.f : (okb ? w : 0.f);                                                           \
         }                                                                                                  \
+        wa.advance();                                                                                      \
+        wb.advance();                                                                                      \
     }
 
     if (k0 < k1) GEMM_ISSUE(k0)
@@ -826,33 +1001,42 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_kernel(const GemmDesc* __re
     const int local = lb - d.blk_begin;
     const int ntile = ((d.M + GEMM_BM - 1) / GEMM_BM) * ((d.N + GEMM_BN - 1) / GEMM_BN);
     const int tile = local % ntile, split = local / ntile;
-#define GEMM_CASE(V, A_, B_, O_, AF_, BF_)                                                          \
-    case (V) * 3 + 0: gemm_body<A_, B_, O_, AF_, BF_, 32>(d, b, tile, split, As, Bs); break;           \
-    case (V) * 3 + 1: gemm_body<A_, B_, O_, AF_, BF_, 64>(d, b, tile, split, As, Bs); break;           \
-    case (V) * 3 + 2: gemm_body<A_, B_, O_, AF_, BF_, 128>(d, b, tile, split, As, Bs); break;
-    switch (d.variant * 3 + d.kdsel) {
+#define GEMM_CASE_P(V, A_, B_, O_, AF_, BF_, P_)                                                    \
+    case (V) * 3 + 0: gemm_body<A_, B_, O_, AF_, BF_, 32, P_>(d, b, tile, split, As, Bs); break;       \
+    case (V) * 3 + 1: gemm_body<A_, B_, O_, AF_, BF_, 64, P_>(d, b, tile, split, As, Bs); break;       \
+    case (V) * 3 + 2: gemm_body<A_, B_, O_, AF_, BF_, 128, P_>(d, b, tile, split, As, Bs); break;
+#define GEMM_CASE(V, A_, B_, O_, AF_, BF_) GEMM_CASE_P(V, A_, B_, O_, AF_, BF_, 0)
+    // a permuted weight's (pb, pc) picks the instantiation here, once per workgroup (gemm_variant admits the model's two only;
+    // the conv's is (14, 5) by construction): GV_COUNT + kdsel stands for the unpitched Linear's (47, 2)
+    int sel = d.variant * 3 + d.kdsel;
+    if (d.variant == GV_LIN_FWD_PERM && perm_case(d.B.pb, d.B.pc) == 2) sel = GV_COUNT * 3 + d.kdsel;
+    switch (sel) {
         GEMM_CASE(GV_LIN_FWD, OPK_DENSE, OPK_DENSE, OUT_STORE, 1, 1)
-        GEMM_CASE(GV_LIN_FWD_PERM, OPK_DENSE, OPK_PERMW, OUT_STORE, 1, 1)
+        GEMM_CASE_P(GV_LIN_FWD_PERM, OPK_DENSE, OPK_PERMW, OUT_STORE, 1, 1, 1)
+        GEMM_CASE_P(GV_COUNT, OPK_DENSE, OPK_PERMW, OUT_STORE, 1, 1, 2)
         GEMM_CASE(GV_LIN_DW, OPK_ACTGRAD, OPK_DENSE, OUT_SLAB, 0, 0)
         GEMM_CASE(GV_LIN_DW_PERM, OPK_ACTGRAD, OPK_DENSE, OUT_PERMW_SLAB, 0, 0)
         GEMM_CASE(GV_LIN_DA, OPK_ACTGRAD, OPK_DENSE, OUT_ACCUM, 1, 0)
-        GEMM_CASE(GV_CONV_FWD, OPK_IM2COL, OPK_PERMW, OUT_CONV, 1, 1)
+        GEMM_CASE_P(GV_CONV_FWD, OPK_IM2COL, OPK_PERMW, OUT_CONV, 1, 1, 1)
         GEMM_CASE(GV_CONV_DW, OPK_CONVGRAD, OPK_IM2COL, OUT_PERMW_SLAB, 1, 0)
         GEMM_CASE(GV_HH_DW, OPK_DENSE, OPK_DENSE, OUT_SLAB, 0, 0)
         GEMM_CASE(GV_LIN_DA_RAW, OPK_DENSE, OPK_DENSE, OUT_ACCUM, 1, 0)
     default: break;
     }
+#undef GEMM_CASE_P
 #undef GEMM_CASE
 }
 
 int gemm_variant(const GemmDesc& g) {
     const int a = g.A.kind, bk = g.B.kind, o = g.out.kind;
     if (a == OPK_DENSE && bk == OPK_DENSE && o == OUT_STORE) return GV_LIN_FWD;
+    // permuted weights: the two permutations the model has (the 32x32 kernel's loaders carry their digits with compile-time radices)
+    if (bk == OPK_PERMW && !perm_case(g.B.pb, g.B.pc)) return -1;
     if (a == OPK_DENSE && bk == OPK_PERMW && o == OUT_STORE) return GV_LIN_FWD_PERM;
     if (a == OPK_ACTGRAD && bk == OPK_DENSE && o == OUT_SLAB) return GV_LIN_DW;
     if (a == OPK_ACTGRAD && bk == OPK_DENSE && o == OUT_PERMW_SLAB) return GV_LIN_DW_PERM;
     if (a == OPK_ACTGRAD && bk == OPK_DENSE && o == OUT_ACCUM) return GV_LIN_DA;
-    if (a == OPK_IM2COL && bk == OPK_PERMW && o == OUT_CONV) return GV_CONV_FWD;
+    if (a == OPK_IM2COL && bk == OPK_PERMW && o == OUT_CONV) return perm_case(g.B.pb, g.B.pc) == 1 ? GV_CONV_FWD : -1;
     if (a == OPK_CONVGRAD && bk == OPK_IM2COL && o == OUT_PERMW_SLAB) return GV_CONV_DW;
     if (a == OPK_DENSE && bk == OPK_DENSE && o == OUT_SLAB) return GV_HH_DW;
     if (a == OPK_DENSE && bk == OPK_DENSE && o == OUT_ACCUM) return GV_LIN_DA_RAW;

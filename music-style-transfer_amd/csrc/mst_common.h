@@ -366,7 +366,7 @@ struct Sizes {
 Sizes mst_sizes(const mst_dims& d);
 
 // ---- launchers (each returns a hipError_t-style int; 0 = ok)
-enum { GV_LIN_FWD, GV_LIN_FWD_PERM, GV_LIN_DW, GV_LIN_DW_PERM, GV_LIN_DA, GV_CONV_FWD, GV_CONV_DW, GV_HH_DW, GV_LIN_DA_RAW };
+enum { GV_LIN_FWD, GV_LIN_FWD_PERM, GV_LIN_DW, GV_LIN_DW_PERM, GV_LIN_DA, GV_CONV_FWD, GV_CONV_DW, GV_HH_DW, GV_LIN_DA_RAW, GV_COUNT };
 int launch_gather(const GatherDesc* dev, int count, int max_rows, Bases b, hipStream_t s);
 int gemm_variant(const GemmDesc& g);
 // descs = clips x members (clip-major); every clip's copy of a member has the same blk_begin inside the clip's block range

@@ -10,6 +10,7 @@
 // offsets relocated to clip k's slices, so the launch count stays that of one clip while every
 // launch carries K times the work.  Clips never mix: `combine`, the loss tree and the LSTM chains are
 // per clip (B = 1 in the reference); only the parameter gradients are summed over clips, in order.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1484,6 +1485,30 @@ void mst_plan::schedule_pass(const std::vector<Step>& seq, std::vector<Step>& ou
             // clip-major replication: clip k's copy of every member, relocated to clip k's workspace slices.
             // The W_hh transpose reads parameters only, so it runs once for all clips.
             // (the multi-workgroup flavour's K_LSTM_T step clears per-clip exchange tags instead: one copy per clip)
+            // One-clip (32x32) GEMM launches dispatch their longest member first: a launch of more than one workgroup per CU runs in
+            // rounds, and a member with a long dependent k chain that starts behind a round of short blocks makes the launch
+            // as long as round + chain.  Stable, by descending k-tiles per workgroup (the kernel's own kchunk / KD), ties to the
+            // accessor kinds that issue more per k-tile.  Members of one launch are independent, and slab offsets were fixed
+            // when the model was emitted: only blk_begin and the block -> member table follow the order.
+            if (ki.fam == F_GEMM && !mfma && !opt.no_merge) {
+                auto ktiles = [&](int idx) {
+                    const GemmDesc& g = gemms.host[idx];
+                    const int kr = (g.K + g.ksplit - 1) / g.ksplit, kd = kr <= 32 ? 32 : (kr <= 64 ? 64 : 128);
+                    return (kr + kd - 1) / kd;
+                };
+                auto dear = [&](int idx) {
+                    switch (gemm_variant(gemms.host[idx])) {
+                    case GV_CONV_FWD: case GV_CONV_DW: return 3;              // im2col / conv-gradient / permuted accessors
+                    case GV_LIN_FWD_PERM: case GV_LIN_DW_PERM: return 2;
+                    case GV_LIN_DW: case GV_LIN_DA: return 1;                 // two loads and the activation derivative per element
+                    default: return 0;
+                    }
+                };
+                std::stable_sort(members.begin(), members.end(), [&](int x, int y) {
+                    const int kx = ktiles(x), ky = ktiles(y);
+                    return kx != ky ? kx > ky : dear(x) > dear(y);
+                });
+            }
             const bool shared_T = s0.kind == K_LSTM_T && !lstms.host[s0.first].multi;
             const int reps = ki.per_clip && !shared_T ? K() : 1;
             if (ki.sched)
@@ -2433,6 +2458,20 @@ extern "C" int32_t mst_plan_step_gemms(const mst_plan* p, int32_t mask, int32_t 
         const GemmDesc& g = p->gemms.sched[s.first + q];
         int32_t* o = out + 6 * n;
         o[0] = g.M; o[1] = g.N; o[2] = g.K; o[3] = g.ksplit; o[4] = g.fold_rows; o[5] = gemm_blocks(g, p->mfma);
+    }
+    return n;
+}
+
+extern "C" int32_t mst_plan_step_gemm_kinds(const mst_plan* p, int32_t mask, int32_t backward, int32_t step, int32_t* out, int32_t cap) {
+    if (!p || !out) return MST_ERR_ARG;
+    const std::vector<const Step*> steps = steps_of(p, mask, backward);
+    if (step < 0 || step >= (int)steps.size()) return MST_ERR_ARG;
+    const Step& s = *steps[step];
+    if (s.kind != K_GEMM && s.kind != K_GEMM_FOLD) return 0;
+    int n = 0;
+    for (int q = 0; q < s.b && n < cap; ++q, ++n) {
+        const GemmDesc& g = p->gemms.sched[s.first + q];
+        out[2 * n] = g.variant; out[2 * n + 1] = p->mfma ? 32 : 32 << g.kdsel;
     }
     return n;
 }

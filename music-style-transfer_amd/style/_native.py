@@ -150,6 +150,8 @@ _SIGS = {
     'mst_plan_step_carrier': (C.c_int32, [_P, C.c_int32, C.c_int32, _P]),
     'mst_plan_set_lstm_small': (C.c_int32, [_P, C.c_int32]),
     'mst_plan_step_gemms': (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32]),
+    'mst_plan_step_gemm_kinds': (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32]),
+    'mst_debug_gemm_walk': (C.c_int64, [C.c_int32] * 11 + [C.POINTER(C.c_int64)]),
     'mst_plan_time_steps': (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P]),
     'mst_audio_plan_create': (_P, [C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32)]),
     'mst_audio_plan_destroy': (None, [_P]),
@@ -475,6 +477,14 @@ class Plan:
         out = np.zeros((cap, 6), np.int32)
         n = self.lib.mst_plan_step_gemms(self.handle, mask, int(backward), step, out.ctypes.data, cap)
         check(n if n < 0 else 0, 'mst_plan_step_gemms')
+        return [tuple(r) for r in out[:n].tolist()]
+
+    def step_gemm_kinds(self, mask, backward, step, cap=2048):
+        """[(kernel variant, k-tile depth)] of the members of GEMM launch step `step`, in step_gemms' order."""
+        import numpy as np
+        out = np.zeros((cap, 2), np.int32)
+        n = self.lib.mst_plan_step_gemm_kinds(self.handle, mask, int(backward), step, out.ctypes.data, cap)
+        check(n if n < 0 else 0, 'mst_plan_step_gemm_kinds')
         return [tuple(r) for r in out[:n].tolist()]
 
     def tiled_train_iteration(self, params, gparams, pitched, unpitched, losses=None, is_root=True, all_reduce=None):

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """What the scheduler decided, one JSON line per plan: tiling, workspace, zero lists and, for every stage mask and both passes,
-each step's shape, carrier reports, launch count and GEMM members.  Plans are built by the CPU interpreter library (no GPU);
+each step's shape, carrier reports, launch count and GEMM members ({M, N, K, k-splits, folded rows, workgroups, kernel
+variant, k-tile depth} each, in the order the launch dispatches them).  Plans are built by the CPU interpreter library (no GPU);
 run it before and after a change to the scheduler and diff the two outputs."""
 import ctypes as C
 import json
@@ -33,14 +34,18 @@ def dump(lib, name, widths, crt, clips, opts):
     for mask in (7, 1, 2, 4):
         for bwd in (0, 1):
             n = lib.mst_plan_step_count(plan, mask, bwd)
-            info, gemms = np.zeros((n, 8), np.int32), np.zeros((4096, 6), np.int32)
+            info, gemms, kinds = np.zeros((n, 8), np.int32), np.zeros((4096, 6), np.int32), np.zeros((4096, 2), np.int32)
             assert lib.mst_plan_step_info(plan, mask, bwd, info.ctypes.data) == n
             cols = {}
             for what in ('carried', 'riders', 'carrier'):
                 out = np.full(n, -9, np.int32)
                 assert getattr(lib, 'mst_plan_step_' + what)(plan, mask, bwd, out.ctypes.data) == n
                 cols['step_' + what] = out.tolist()
-            members = [gemms[:lib.mst_plan_step_gemms(plan, mask, bwd, i, gemms.ctypes.data, len(gemms))].tolist() for i in range(n)]
+            members = []
+            for i in range(n):
+                m = lib.mst_plan_step_gemms(plan, mask, bwd, i, gemms.ctypes.data, len(gemms))
+                assert lib.mst_plan_step_gemm_kinds(plan, mask, bwd, i, kinds.ctypes.data, len(kinds)) == m
+                members.append(np.concatenate([gemms[:m], kinds[:m]], axis=1).tolist())
             assert all(bool(m) == (k in (K_GEMM, K_GEMM_FOLD)) for m, k in zip(members, info[:, 5].tolist()))
             row['mask%d_%s' % (mask, 'bwd' if bwd else 'fwd')] = dict(step_info=info.tolist(), launch_count=lib.mst_plan_launch_count(plan, mask, bwd),
                                                                    step_gemms=members, **cols)
