@@ -303,6 +303,25 @@ int32_t mst_roll_count(const float* x, int64_t n_cells, int32_t nfeat, int32_t m
 int32_t mst_roll_compact(const float* x, int64_t n_cells, int32_t nfeat, int32_t mode, const int32_t* ws,
                          int64_t capacity, int32_t* cells, float* feats, mst_stream stream);
 
+/* The batched, strided twins: n_rolls rolls compacted at once, in the record layout mst_clip_scatter consumes.  Roll k is the
+ * n_cells x nfeat floats at x + k * roll_stride (the K predictions of a batched plan lie mst_plan_layout's clip stride apart in
+ * its workspace); the floats between two rolls are never read.  The 16-byte phase of a roll is its own: roll_stride need not be
+ * a multiple of 4.  Modes and record predicates are those above.
+ * mst_rolls_count leaves in row k of ws (n_rolls rows of mst_roll_slices(n_cells) + 1 int32) exactly what mst_roll_count leaves
+ * for that roll.  mst_rolls_compact, given that ws, writes the record of rank r < capacity of roll k to cells[k * capacity + r]
+ * (the cell index within the roll, strictly ascending in r) and feats[(k * capacity + r) * nfeat ...], and the roll's TRUE number
+ * of records to counts[k]: the caller sees an overflow, and mst_clip_scatter clamps the count.  Records of rank >= capacity are
+ * dropped, never stored: of row k nothing beyond min(counts[k], capacity) records is written, x and ws are read only, and with
+ * capacity = 0 only counts is written.  One launch and one scan launch (a workgroup per roll) for the count, one launch for the
+ * compaction — the count's first and the compaction's launch once per 65535 rolls, as mst_roll_metrics; enqueue-only on `stream` (no allocation, no host synchronisation,
+ * capturable as a single chain); no atomics, no workgroup waits for another: the same bits on every run.  x needs float
+ * alignment only.  MST_ERR_ARG, and nothing is launched: null pointer, n_rolls < 1, n_cells < 1 or >= 2^31, n_rolls x slices >=
+ * 2^31, nfeat outside {2, 5}, mode outside {0, 1}, capacity < 0, roll_stride < n_cells * nfeat, x not 4-byte aligned. */
+int32_t mst_rolls_count(const float* x, int64_t roll_stride, int32_t n_rolls, int64_t n_cells, int32_t nfeat, int32_t mode,
+                        int32_t* ws /* n_rolls x (mst_roll_slices(n_cells) + 1) */, mst_stream stream);
+int32_t mst_rolls_compact(const float* x, int64_t roll_stride, int32_t n_rolls, int64_t n_cells, int32_t nfeat, int32_t mode,
+                          const int32_t* ws, int32_t capacity, int32_t* cells, float* feats, int32_t* counts, mst_stream stream);
+
 /* ---- note metrics: how good are hard_output's decisions?  No reference counterpart: the reference has no validation, and
  * get_total_loss (style/model.py:935-997) reports soft quantities only — its smooth F1 is computed on raw velocities, while the
  * inference driver writes hard_output's decisions (style/model.py:818-832) to MIDI.
@@ -396,6 +415,43 @@ int32_t mst_eval_accumulate(const float* losses   /* n_clips x MST_N_LOSSES */,
                             int32_t n_clips, int32_t channels,
                             const int32_t* live   /* DEVICE, one int32, or NULL = all */,
                             double* acc /* MST_EVAL_ACC_WORDS, 8-byte aligned */, mst_stream stream);
+
+/* ---- batched style transfer: clip k of a batch rendered with the style of clip donors[k] of the same batch, and a score of the
+ * swap, without leaving the device.  No reference counterpart: the reference transfers one style onto one song per call
+ * (style/style_transfer.py) and has no measure of the result.  Both entry points are one launch, enqueue-only on `stream` (no
+ * allocation, no host synchronisation, capturable as a single chain), without atomics and without a workgroup waiting for
+ * another: the same bits on every run.
+ *
+ * mst_clip_gather: rows of `src` (src_rows runs of len floats, src_stride floats apart) into per-clip destinations by a device
+ * index.  For clip k < n_clips and i < len:
+ *     dst[k * dst_stride + i] = src[idx[k] * src_stride + i]          copied bit for bit
+ * idx (a DEVICE array of n_clips int32, read ON THE DEVICE as mst_window_inputs reads its rows: a captured launch serves other
+ * donors) may be NULL: idx[k] = k.  An idx[k] outside [0, src_rows) writes quiet NaNs (0x7fc00000) into that clip's len floats
+ * instead, and src is not read for it.  Every named float of dst is written exactly once and nothing else is written; src is read
+ * only; float alignment only.  src_stride = 0 is allowed (every row is the same run).
+ * MST_ERR_ARG, and nothing is launched: a null src or dst; n_clips, src_rows or len < 1; a negative stride; dst_stride < len with
+ * n_clips > 1 (the destinations would overlap); the ranges [src, src + (src_rows - 1) * src_stride + len) and [dst, dst +
+ * (n_clips - 1) * dst_stride + len) intersecting (a permutation in place is a race: go through a side buffer) or not
+ * representable; src / dst not 4-byte aligned; more than 2^31 - 1 chunks of 1024 floats in all. */
+int32_t mst_clip_gather(const float* src, int32_t src_rows, int64_t src_stride, float* dst, int64_t dst_stride,
+                        const int32_t* idx /* DEVICE int32[n_clips] or NULL = identity */, int32_t n_clips, int64_t len,
+                        mst_stream stream);
+
+/* mst_style_sums: the raw material of three cosines per clip.  With x = a + k * a_stride, y = b + idx[k] * b_stride and
+ * z = b + k * b_stride (len floats each; idx as above, NULL = identity), the MST_STYLE_SUM_WORDS doubles of out[k] are
+ *   [0] sum x.x   [1] sum y.y   [2] sum z.z   [3] sum x.y   [4] sum x.z   [5] sum y.z   [6] len   [7] 0
+ * Each sum is a left-to-right float64 sum over i = 0 ... len - 1 that starts from 0; a term is the product of the two floats
+ * widened to double, which is exact: the bits a host loop of double additions in that order gives.  One workgroup of 64 lanes
+ * per clip, lane w < 6 owns word w.  An idx[k] outside [0, b_rows) makes words 1, 3 and 5 of that clip NaN, a k >= b_rows words
+ * 2, 4 and 5; the other words stay right and b is not read outside its rows.  Every word of out[0, n_clips x 8) and nothing
+ * beyond it is written; a and b are read only (they may overlap) and need float alignment only.  Quotients and square roots are
+ * the host's (style.metrics.style_cosines), so the device result stays bit-checkable.
+ * MST_ERR_ARG, and nothing is launched: a null a, b or out; n_clips or b_rows < 1; len < 1 or >= 2^31; a negative stride; a / b
+ * not 4-byte aligned; out not 8-byte aligned. */
+#define MST_STYLE_SUM_WORDS 8
+int32_t mst_style_sums(const float* a, int64_t a_stride, const float* b, int32_t b_rows, int64_t b_stride,
+                       const int32_t* idx /* DEVICE int32[n_clips] or NULL = identity */, int32_t n_clips, int64_t len,
+                       double* out /* n_clips x MST_STYLE_SUM_WORDS, 8-byte aligned */, mst_stream stream);
 
 /* ---- instrumentation (bench.py only; synchronises on HIP events, never used for training):
  * average duration of every launch step of a pass, with its algorithmic FLOPs and bytes.

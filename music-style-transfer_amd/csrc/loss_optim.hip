@@ -978,15 +978,15 @@ extern "C" int64_t mst_roll_slices(int64_t n_cells) {
     return (n_cells + ROLL_SLICE - 1) / ROLL_SLICE;
 }
 
-// Stages slice blockIdx.x into LDS and returns its number of cells (the last slice is ragged).  g = flat float index + shift,
+// Stages slice `slice` into LDS and returns its number of cells (the last slice is ragged).  g = flat float index + shift,
 // shift = floats between the previous 16-byte boundary and x, so that g = 0 (mod 4) is a 16-byte-aligned address whatever the
 // alignment of x.  img4 holds g in [gb, gb + ROLL_SLICE * NFEAT + 4); cell c of the slice starts at float shift + c * NFEAT of it.
 // Only floats of x are read: a group of four that is not wholly inside the slice takes scalar loads.
 template <int NFEAT>
-__device__ __forceinline__ int roll_stage(const float* x, int64_t n_cells, int shift, roll_f4* img4) {
+__device__ __forceinline__ int roll_stage(const float* x, int64_t n_cells, int shift, roll_f4* img4, int slice = blockIdx.x) {
     float* img = reinterpret_cast<float*>(img4);
     const MST_GLOBAL_AS float* xg = (const MST_GLOBAL_AS float*)x;
-    const int64_t c0 = (int64_t)blockIdx.x * ROLL_SLICE;
+    const int64_t c0 = (int64_t)slice * ROLL_SLICE;
     const int cells = (int)(n_cells - c0 < ROLL_SLICE ? n_cells - c0 : ROLL_SLICE);
     const int64_t gb = c0 * NFEAT, g0 = gb + shift, g1 = g0 + (int64_t)cells * NFEAT;
     for (int i = threadIdx.x; i < ROLL_SLICE * NFEAT / 4 + 1; i += ROLL_THREADS) {
@@ -1041,11 +1041,12 @@ __device__ __forceinline__ int roll_wave_scan(int v, int lane) {
 // costs two LDS cycles per read.
 #define ROLL_CELL(wave, j, lane) ((wave) * (64 * ROLL_PER_LANE) + (j) * 64 + (lane))
 
+// the records of slice `slice` of the roll at x, counted into ws[slice]: the body of the one-roll and of the batched kernel
 template <int NFEAT>
-__global__ __launch_bounds__(ROLL_THREADS) void roll_count_kernel(const float* x, int64_t n_cells, int shift, int mode, int32_t* ws) {
+__device__ __forceinline__ void roll_count_slice(const float* x, int64_t n_cells, int shift, int mode, int slice, int32_t* ws) {
     __shared__ roll_f4 img4[ROLL_SLICE * NFEAT / 4 + 1];
     __shared__ int wtot[ROLL_WAVES];
-    const int cells = roll_stage<NFEAT>(x, n_cells, shift, img4);
+    const int cells = roll_stage<NFEAT>(x, n_cells, shift, img4, slice);
     const float* img = reinterpret_cast<const float*>(img4) + shift;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     int n = 0;
@@ -1062,12 +1063,27 @@ __global__ __launch_bounds__(ROLL_THREADS) void roll_count_kernel(const float* x
     if (threadIdx.x == 0) {
         int total = 0;
         for (int w = 0; w < ROLL_WAVES; ++w) total += wtot[w];
-        ws[blockIdx.x] = total;
+        ws[slice] = total;
     }
 }
 
+template <int NFEAT>
+__global__ __launch_bounds__(ROLL_THREADS) void roll_count_kernel(const float* x, int64_t n_cells, int shift, int mode, int32_t* ws) {
+    roll_count_slice<NFEAT>(x, n_cells, shift, mode, blockIdx.x, ws);
+}
+
+// The batched twin: workgroup (s, y) owns slice s of roll r0 + y, the n_cells x NFEAT floats at x + (r0 + y) * roll_stride, and
+// row r0 + y of ws (slices + 1 words).  The roll's 16-byte phase is its own: roll_stride need not be a multiple of 4.
+template <int NFEAT>
+__global__ __launch_bounds__(ROLL_THREADS) void rolls_count_kernel(const float* x, int64_t roll_stride, int64_t r0, int64_t n_cells, int mode,
+                                                                   int32_t* ws) {
+    const int64_t k = r0 + blockIdx.y;
+    const float* xk = x + k * roll_stride;
+    roll_count_slice<NFEAT>(xk, n_cells, (int)(((uintptr_t)xk & 15) / 4), mode, blockIdx.x, ws + k * ((int64_t)gridDim.x + 1));
+}
+
 // one workgroup: ws[0, n) from per-slice counts to their exclusive prefix, in place and in order; ws[n] = the total
-__global__ __launch_bounds__(ROLL_THREADS) void roll_scan_kernel(int32_t* ws, int n) {
+__device__ __forceinline__ void roll_scan_row(int32_t* ws, int n) {
     __shared__ int wtot[ROLL_WAVES];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     int carry = 0;
@@ -1098,15 +1114,23 @@ __global__ __launch_bounds__(ROLL_THREADS) void roll_scan_kernel(int32_t* ws, in
     if (tid == 0) ws[n] = carry;
 }
 
+__global__ __launch_bounds__(ROLL_THREADS) void roll_scan_kernel(int32_t* ws, int n) { roll_scan_row(ws, n); }
+
+// the batched twin: workgroup k scans row k of ws (n + 1 words)
+__global__ __launch_bounds__(ROLL_THREADS) void rolls_scan_kernel(int32_t* ws, int n) {
+    roll_scan_row(ws + (int64_t)blockIdx.x * ((int64_t)n + 1), n);
+}
+
+// the records of slice `slice` of the roll at x, written behind those of the slices before it: the body of both emit kernels
 template <int NFEAT>
-__global__ __launch_bounds__(ROLL_THREADS) void roll_emit_kernel(const float* x, int64_t n_cells, int shift, int mode, const int32_t* ws,
-                                                                 int64_t capacity, int32_t* cells_out, float* feats) {
+__device__ __forceinline__ void roll_emit_slice(const float* x, int64_t n_cells, int shift, int mode, int slice, const int32_t* ws,
+                                                int64_t capacity, int32_t* cells_out, float* feats) {
     __shared__ roll_f4 img4[ROLL_SLICE * NFEAT / 4 + 1];
     __shared__ int32_t rec[ROLL_SLICE];
     __shared__ int wtot[ROLL_WAVES];
-    const int base = ws[blockIdx.x];                               // records in the slices before this one
-    if (base < 0 || base >= capacity || ws[blockIdx.x + 1] == base) return;     // nothing of this slice is stored (workgroup-uniform)
-    const int cells = roll_stage<NFEAT>(x, n_cells, shift, img4);
+    const int base = ws[slice];                                    // records in the slices before this one
+    if (base < 0 || base >= capacity || ws[slice + 1] == base) return;          // nothing of this slice is stored (workgroup-uniform)
+    const int cells = roll_stage<NFEAT>(x, n_cells, shift, img4, slice);
     float* img = reinterpret_cast<float*>(img4);
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     // one byte per j: is the lane's j-th cell a record?  Scanned over the wave as one integer (a byte counts to 64 at most).
@@ -1126,7 +1150,7 @@ __global__ __launch_bounds__(ROLL_THREADS) void roll_emit_kernel(const float* x,
         if (w < wave) rank += wtot[w];
         count += wtot[w];
     }
-    const int32_t c0 = (int32_t)((int64_t)blockIdx.x * ROLL_SLICE);
+    const int32_t c0 = (int32_t)((int64_t)slice * ROLL_SLICE);
 #pragma unroll
     for (int j = 0; j < ROLL_PER_LANE; ++j) {                      // cell order within the wave: j, then lane
         if ((mine >> (8 * j)) & 1) {
@@ -1143,6 +1167,26 @@ __global__ __launch_bounds__(ROLL_THREADS) void roll_emit_kernel(const float* x,
     for (int i = tid; i < keep; i += ROLL_THREADS) cells_out[base + i] = rec[i];
     float* dst = feats + (int64_t)base * NFEAT;
     for (int i = tid; i < keep * NFEAT; i += ROLL_THREADS) dst[i] = img[i];
+}
+
+template <int NFEAT>
+__global__ __launch_bounds__(ROLL_THREADS) void roll_emit_kernel(const float* x, int64_t n_cells, int shift, int mode, const int32_t* ws,
+                                                                 int64_t capacity, int32_t* cells_out, float* feats) {
+    roll_emit_slice<NFEAT>(x, n_cells, shift, mode, blockIdx.x, ws, capacity, cells_out, feats);
+}
+
+// The batched twin: workgroup (s, y) emits slice s of roll k = r0 + y into row k of cells / feats (capacity records each).  The
+// first workgroup of a roll also leaves the roll's TRUE total in counts[k], before anything can make it return.
+template <int NFEAT>
+__global__ __launch_bounds__(ROLL_THREADS) void rolls_emit_kernel(const float* x, int64_t roll_stride, int64_t r0, int64_t n_cells, int mode,
+                                                                  const int32_t* ws, int capacity, int32_t* cells_out, float* feats,
+                                                                  int32_t* counts) {
+    const int64_t k = r0 + blockIdx.y;
+    const float* xk = x + k * roll_stride;
+    const int32_t* wsk = ws + k * ((int64_t)gridDim.x + 1);
+    if (blockIdx.x == 0 && threadIdx.x == 0) counts[k] = wsk[gridDim.x];
+    roll_emit_slice<NFEAT>(xk, n_cells, (int)(((uintptr_t)xk & 15) / 4), mode, blockIdx.x, wsk, capacity, cells_out + k * capacity,
+                           feats + k * capacity * NFEAT);
 }
 
 static bool roll_args_ok(const float* x, int64_t n_cells, int32_t nfeat, int32_t mode) {
@@ -1174,6 +1218,50 @@ extern "C" int32_t mst_roll_compact(const float* x, int64_t n_cells, int32_t nfe
         hipLaunchKernelGGL(roll_emit_kernel<5>, dim3(nb), dim3(ROLL_THREADS), 0, s, x, n_cells, shift, (int)mode, ws, capacity, cells, feats);
     else
         hipLaunchKernelGGL(roll_emit_kernel<2>, dim3(nb), dim3(ROLL_THREADS), 0, s, x, n_cells, shift, (int)mode, ws, capacity, cells, feats);
+    return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
+}
+
+// ---- the batched, strided twins (mst_rolls_count, mst_rolls_compact): the K prediction rolls of a batched plan lie clip_stride
+// floats apart in its workspace; one grid takes them all, the roll in blockIdx.y.
+#define ROLLS_MAX_GRID_Y 65535   // rolls one launch takes in blockIdx.y; more rolls are more launches of the same chain
+
+static bool rolls_args_ok(const float* x, int64_t roll_stride, int32_t n_rolls, int64_t n_cells, int32_t nfeat, int32_t mode) {
+    return roll_args_ok(x, n_cells, nfeat, mode) && n_rolls >= 1 && roll_stride >= n_cells * nfeat &&
+           (int64_t)n_rolls * mst_roll_slices(n_cells) < ((int64_t)1 << 31);
+}
+
+extern "C" int32_t mst_rolls_count(const float* x, int64_t roll_stride, int32_t n_rolls, int64_t n_cells, int32_t nfeat, int32_t mode,
+                                   int32_t* ws, mst_stream stream) {
+    if (!rolls_args_ok(x, roll_stride, n_rolls, n_cells, nfeat, mode) || !ws) return MST_ERR_ARG;
+    const unsigned nb = (unsigned)mst_roll_slices(n_cells);
+    hipStream_t s = (hipStream_t)stream;
+    for (int64_t r0 = 0; r0 < n_rolls; r0 += ROLLS_MAX_GRID_Y) {
+        const unsigned ny = (unsigned)(n_rolls - r0 < ROLLS_MAX_GRID_Y ? n_rolls - r0 : ROLLS_MAX_GRID_Y);
+        if (nfeat == 5)
+            hipLaunchKernelGGL(rolls_count_kernel<5>, dim3(nb, ny), dim3(ROLL_THREADS), 0, s, x, roll_stride, r0, n_cells, (int)mode, ws);
+        else
+            hipLaunchKernelGGL(rolls_count_kernel<2>, dim3(nb, ny), dim3(ROLL_THREADS), 0, s, x, roll_stride, r0, n_cells, (int)mode, ws);
+    }
+    hipLaunchKernelGGL(rolls_scan_kernel, dim3((unsigned)n_rolls), dim3(ROLL_THREADS), 0, s, ws, (int)nb);
+    return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
+}
+
+extern "C" int32_t mst_rolls_compact(const float* x, int64_t roll_stride, int32_t n_rolls, int64_t n_cells, int32_t nfeat, int32_t mode,
+                                     const int32_t* ws, int32_t capacity, int32_t* cells, float* feats, int32_t* counts,
+                                     mst_stream stream) {
+    if (!rolls_args_ok(x, roll_stride, n_rolls, n_cells, nfeat, mode) || !ws || !cells || !feats || !counts || capacity < 0)
+        return MST_ERR_ARG;
+    const unsigned nb = (unsigned)mst_roll_slices(n_cells);
+    hipStream_t s = (hipStream_t)stream;
+    for (int64_t r0 = 0; r0 < n_rolls; r0 += ROLLS_MAX_GRID_Y) {
+        const unsigned ny = (unsigned)(n_rolls - r0 < ROLLS_MAX_GRID_Y ? n_rolls - r0 : ROLLS_MAX_GRID_Y);
+        if (nfeat == 5)
+            hipLaunchKernelGGL(rolls_emit_kernel<5>, dim3(nb, ny), dim3(ROLL_THREADS), 0, s, x, roll_stride, r0, n_cells, (int)mode, ws,
+                               (int)capacity, cells, feats, counts);
+        else
+            hipLaunchKernelGGL(rolls_emit_kernel<2>, dim3(nb, ny), dim3(ROLL_THREADS), 0, s, x, roll_stride, r0, n_cells, (int)mode, ws,
+                               (int)capacity, cells, feats, counts);
+    }
     return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
 }
 
@@ -1531,5 +1619,91 @@ extern "C" int32_t mst_eval_accumulate(const float* losses, const double* metric
         return MST_ERR_ARG;
     hipLaunchKernelGGL(eval_accumulate_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, losses, metrics, (int)n_clips, (int)channels,
                        live, acc);
+    return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
+}
+
+// ------------------------------------------------------------------ batched style transfer (mst_clip_gather, mst_style_sums)
+// The two small launches that let a style swap and its score stay on the device.  Like the windowed evaluation's they are
+// latency-bound and owe exactness: a bit copy by a device index, and six left-to-right float64 sums per clip.
+#define CG_THREADS 256
+#define CG_CHUNK 1024        // floats of a clip one workgroup copies
+
+// workgroup b: chunk b % chunks of clip b / chunks.  The index is one load per workgroup, as in window_inputs_kernel.
+__global__ __launch_bounds__(CG_THREADS) void clip_gather_kernel(const uint32_t* src, int src_rows, int64_t src_stride, uint32_t* dst,
+                                                                 int64_t dst_stride, const int32_t* idx, int chunks, int64_t len) {
+    const int k = blockIdx.x / chunks;
+    const int64_t c0 = (int64_t)(blockIdx.x % chunks) * CG_CHUNK;
+    const int64_t c1 = c0 + CG_CHUNK < len ? c0 + CG_CHUNK : len;
+    const int row = idx ? MST_UNIFORM(idx[k]) : k;
+    const bool ok = row >= 0 && row < src_rows;                 // a row outside src is never read: quiet NaNs instead
+    const uint32_t* from = src + (ok ? (int64_t)row * src_stride : 0);
+    uint32_t* to = dst + (int64_t)k * dst_stride;
+    for (int64_t i = c0 + threadIdx.x; i < c1; i += CG_THREADS) to[i] = ok ? from[i] : 0x7fc00000u;
+}
+
+// floats from the first to one past the last of `rows` runs of `len` floats, `stride` apart; false when that overflows
+static bool span_floats(int64_t rows, int64_t stride, int64_t len, int64_t* span) {
+    int64_t s;
+    return !__builtin_mul_overflow(rows - 1, stride, &s) && !__builtin_add_overflow(s, len, span) && *span < ((int64_t)1 << 60);
+}
+
+extern "C" int32_t mst_clip_gather(const float* src, int32_t src_rows, int64_t src_stride, float* dst, int64_t dst_stride,
+                                   const int32_t* idx, int32_t n_clips, int64_t len, mst_stream stream) {
+    if (!src || !dst || n_clips < 1 || src_rows < 1 || len < 1 || src_stride < 0 || dst_stride < 0 || (dst_stride < len && n_clips > 1) ||
+        ((uintptr_t)src & 3) || ((uintptr_t)dst & 3))
+        return MST_ERR_ARG;
+    int64_t src_span, dst_span;
+    if (!span_floats(src_rows, src_stride, len, &src_span) || !span_floats(n_clips, dst_stride, len, &dst_span)) return MST_ERR_ARG;
+    const uintptr_t s0 = (uintptr_t)src, s1 = s0 + 4 * (uintptr_t)src_span, d0 = (uintptr_t)dst, d1 = d0 + 4 * (uintptr_t)dst_span;
+    if (s0 < d1 && d0 < s1) return MST_ERR_ARG;                 // a permutation in place is a race: go through a side buffer
+    const int64_t chunks = (len + CG_CHUNK - 1) / CG_CHUNK;
+    if (chunks * n_clips > 0x7fffffff) return MST_ERR_ARG;
+    hipLaunchKernelGGL(clip_gather_kernel, dim3((unsigned)(chunks * n_clips)), dim3(CG_THREADS), 0, (hipStream_t)stream,
+                       (const uint32_t*)src, (int)src_rows, src_stride, (uint32_t*)dst, dst_stride, idx, (int)chunks, len);
+    return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
+}
+
+// One 64-lane workgroup per clip; lane w < 6 owns word w and adds its products left to right in float64.  As in
+// eval_accumulate_kernel the loads do not depend on the add chains: all 64 lanes copy the next stretch of x, y and z into LDS
+// and the six owners then walk it in order.  The product of two floats widened to double is exact (48 significant bits, and no
+// float product leaves double's range), so whether the compiler contracts the multiply and the add changes no bit.
+#define SS_CHUNK 1024        // floats of each of the three vectors per stretch: 12 KB of LDS
+
+__global__ __launch_bounds__(64) void style_sums_kernel(const float* a, int64_t a_stride, const float* b, int b_rows, int64_t b_stride,
+                                                        const int32_t* idx, int64_t len, double* out) {
+    __shared__ float sm[3][SS_CHUNK];
+    const int k = blockIdx.x, w = threadIdx.x;
+    const int row = idx ? MST_UNIFORM(idx[k]) : k;
+    const bool y_ok = row >= 0 && row < b_rows, z_ok = k < b_rows;      // a row outside b is never read: its words are NaN
+    const float* x = a + (int64_t)k * a_stride;
+    const float* v[3] = {x, y_ok ? b + (int64_t)row * b_stride : x, z_ok ? b + (int64_t)k * b_stride : x};
+    const int pa = (w == 0 || w == 3 || w == 4) ? 0 : (w == 1 || w == 5) ? 1 : 2;
+    const int pb = w == 0 ? 0 : (w == 1 || w == 3) ? 1 : 2;
+    double sum = 0.0;
+    for (int64_t i0 = 0; i0 < len; i0 += SS_CHUNK) {                    // workgroup-uniform
+        const int n = (int)(len - i0 < SS_CHUNK ? len - i0 : SS_CHUNK);
+        for (int q = 0; q < 3; ++q)
+            for (int i = w; i < n; i += 64) sm[q][i] = v[q][i0 + i];
+        __syncthreads();
+        if (w < 6) {
+#pragma unroll 8
+            for (int i = 0; i < n; ++i) sum += (double)sm[pa][i] * (double)sm[pb][i];
+        }
+        __syncthreads();                                                // sm is rewritten by the next stretch
+    }
+    const bool uses_y = w == 1 || w == 3 || w == 5, uses_z = w == 2 || w == 4 || w == 5;
+    if ((uses_y && !y_ok) || (uses_z && !z_ok)) sum = __builtin_nan("");
+    if (w < 6) out[(int64_t)k * 8 + w] = sum;
+    if (w == 6) out[(int64_t)k * 8 + 6] = (double)len;
+    if (w == 7) out[(int64_t)k * 8 + 7] = 0.0;
+}
+
+extern "C" int32_t mst_style_sums(const float* a, int64_t a_stride, const float* b, int32_t b_rows, int64_t b_stride, const int32_t* idx,
+                                  int32_t n_clips, int64_t len, double* out, mst_stream stream) {
+    if (!a || !b || !out || n_clips < 1 || b_rows < 1 || len < 1 || len >= ((int64_t)1 << 31) || a_stride < 0 || b_stride < 0 ||
+        ((uintptr_t)a & 3) || ((uintptr_t)b & 3) || ((uintptr_t)out & 7))
+        return MST_ERR_ARG;
+    hipLaunchKernelGGL(style_sums_kernel, dim3((unsigned)n_clips), dim3(64), 0, (hipStream_t)stream, a, a_stride, b, (int)b_rows, b_stride,
+                       idx, len, out);
     return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
 }

@@ -48,6 +48,7 @@ ROLL_NONZERO, ROLL_HARD = 0, 1      # mst_amd.h MST_ROLL_*: record modes of mst_
 WINDOW_WORDS = 4                    # mst_amd.h mst_window: int32 words per descriptor of mst_clip_window (first, count, src_bars, r0)
 METRIC_WORDS = 8                    # mst_amd.h MST_METRIC_WORDS: doubles per record of mst_roll_metrics / mst_eval_iteration
 ROW_FIELDS = 8                      # mst_amd.h MST_ROW_FIELDS: pieces of a table row one mst_window_inputs call places
+STYLE_SUM_WORDS = 8                 # mst_amd.h MST_STYLE_SUM_WORDS: doubles per clip of mst_style_sums
 EVAL_ACC_WORDS = 41                 # mst_amd.h MST_EVAL_ACC_WORDS: doubles of a round's running sum (mst_eval_accumulate)
 
 
@@ -136,6 +137,10 @@ _SIGS = {
     'mst_roll_slices': (C.c_int64, [C.c_int64]),
     'mst_roll_count': (C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
     'mst_roll_compact': (C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P]),
+    'mst_rolls_count': (C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
+    'mst_rolls_compact': (C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, _P]),
+    'mst_clip_gather': (C.c_int32, [_P, C.c_int32, C.c_int64, _P, C.c_int64, _P, C.c_int32, C.c_int64, _P]),
+    'mst_style_sums': (C.c_int32, [_P, C.c_int64, _P, C.c_int32, C.c_int64, _P, C.c_int32, C.c_int64, _P, _P]),
     'mst_roll_metrics_scratch_bytes': (C.c_int64, [C.c_int64, C.c_int64]),
     'mst_roll_metrics': (C.c_int32, [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P]),
     'mst_eval_scratch_bytes': (C.c_int64, [_P]),
@@ -249,6 +254,37 @@ class Native:
         addr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()
         check(self.lib.mst_roll_compact(addr(x), int(n_cells), int(nfeat), int(mode), addr(ws), int(capacity), addr(cells), addr(feats),
                                         stream), 'mst_roll_compact')
+
+    def rolls_count(self, x, roll_stride, n_rolls, n_cells, nfeat, mode, ws, stream=None):
+        """mst_rolls_count: roll_count of the `n_rolls` rolls at x + k * roll_stride floats (n_cells x nfeat floats each) into row
+        k of `ws` (int32, n_rolls x (roll_slices(n_cells) + 1)).  Tensors on one device or raw addresses.  Enqueue-only."""
+        addr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()
+        check(self.lib.mst_rolls_count(addr(x), int(roll_stride), int(n_rolls), int(n_cells), int(nfeat), int(mode), addr(ws), stream),
+              'mst_rolls_count')
+
+    def rolls_compact(self, x, roll_stride, n_rolls, n_cells, nfeat, mode, ws, capacity, cells, feats, counts, stream=None):
+        """mst_rolls_compact: after rolls_count on the same rolls, write the records of rank < `capacity` of roll k to row k of
+        `cells` (int32, n_rolls x capacity) and `feats` (float32, n_rolls x capacity x nfeat), and the roll's true number of
+        records to counts[k] (int32): mst_clip_scatter's layout.  Tensors on x's device or raw addresses.  Enqueue-only."""
+        addr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()
+        check(self.lib.mst_rolls_compact(addr(x), int(roll_stride), int(n_rolls), int(n_cells), int(nfeat), int(mode), addr(ws),
+                                         int(capacity), addr(cells), addr(feats), addr(counts), stream), 'mst_rolls_compact')
+
+    def clip_gather(self, src, src_rows, src_stride, dst, dst_stride, idx, n_clips, length, stream=None):
+        """mst_clip_gather: dst[k * dst_stride + i] = src[idx[k] * src_stride + i] for k < n_clips, i < length, bit for bit.
+        `idx` (int32, n_clips) is read on the device, None = identity; an index outside [0, src_rows) gives quiet NaNs.
+        Tensors on one device or raw addresses.  Enqueue-only."""
+        addr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()
+        check(self.lib.mst_clip_gather(addr(src), int(src_rows), int(src_stride), addr(dst), int(dst_stride), addr(idx), int(n_clips),
+                                       int(length), stream), 'mst_clip_gather')
+
+    def style_sums(self, a, a_stride, b, b_rows, b_stride, idx, n_clips, length, out, stream=None):
+        """mst_style_sums: per clip k the six float64 dot products of x = a + k * a_stride, y = b + idx[k] * b_stride and
+        z = b + k * b_stride (`length` floats each) into out[k] (STYLE_SUM_WORDS float64): xx, yy, zz, xy, xz, yz, length, 0.
+        `idx` as for clip_gather.  Tensors on one device or raw addresses.  Enqueue-only."""
+        addr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()
+        check(self.lib.mst_style_sums(addr(a), int(a_stride), addr(b), int(b_rows), int(b_stride), addr(idx), int(n_clips), int(length),
+                                      addr(out), stream), 'mst_style_sums')
 
     def roll_metrics_scratch_bytes(self, n_groups, group_cells):
         n = self.lib.mst_roll_metrics_scratch_bytes(int(n_groups), int(group_cells))

@@ -159,6 +159,44 @@ class EvalResult:
         return SongInfoMetrics.from_device(self.metrics[-1])
 
 
+class TransferResult:
+    """What StyleTransferModel.transfer_windows returns for its K clips.  `instruments_pred` (K, 41), `mode_pred` (K, 2) and
+    `bpm_pred` (K,) are on the device; `pitched` / `unpitched` are K host SparseRolls each ((1, C, R, T, 10, 56, 5) /
+    (1, 1, R, T, 10, 47, 2); `unpitched` is None without percussion): hard_output's note records of the rendered clips.  With
+    score=True `style_sums` (K, 8 float64, mst_style_sums' words) and `retention` (K, C + 1, 8 float64, mst_roll_metrics records
+    of the written rolls against the clips' own notes: the C pitched channels, then the unpitched roll — zeros without
+    percussion) are on the device, else None.  Every tensor is the result's own: a later call does not change it."""
+
+    def __init__(self, instruments_pred, mode_pred, bpm_pred, pitched, unpitched, style_sums=None, retention=None):
+        self.instruments_pred, self.mode_pred, self.bpm_pred = instruments_pred, mode_pred, bpm_pred
+        self.pitched, self.unpitched, self.style_sums, self.retention = pitched, unpitched, style_sums, retention
+
+    @property
+    def cosines(self):
+        return style_cosines(self.style_sums)
+
+    @property
+    def pitched_retention(self):
+        return NoteMetrics(self.retention[:, :-1])
+
+    @property
+    def unpitched_retention(self):
+        return NoteMetrics(self.retention[:, -1])
+
+
+def style_cosines(style_sums):
+    """mst_style_sums' words (..., 8) -> the three cosines (..., 3) as host float64: the rendered clip's style against the
+    donor's (did the style arrive?), against the clip's own (what is left of it), and the clip's own against the donor's — the
+    baseline both are read against.  NaN where a norm is 0."""
+    s = np.asarray(style_sums.detach().cpu() if torch.is_tensor(style_sums) else style_sums, dtype=np.float64)
+    if s.shape[-1] != _native.STYLE_SUM_WORDS:
+        raise ValueError(f'style_cosines takes (..., {_native.STYLE_SUM_WORDS}) words, not {s.shape}')
+    xx, yy, zz, xy, xz, yz = (s[..., i] for i in range(6))
+    with np.errstate(invalid='ignore', divide='ignore'):
+        cos = lambda dot, a, b: np.where((a > 0) & (b > 0), dot / (np.sqrt(a) * np.sqrt(b)), np.nan)
+        return np.stack([cos(xy, xx, yy), cos(xz, xx, zz), cos(yz, yy, zz)], axis=-1)
+
+
 def note_metrics(pred, target, per_channel=False):
     """NoteMetrics of two GPU rolls of the model's shapes — (1, C, R, T, 10, 56, 5) or (1, 1, R, T, 10, 47, 2) — as
     get_total_loss is the stand-alone loss.  per_channel=True keeps one record per channel (the roll's second axis), else the

@@ -666,6 +666,175 @@ class StyleTransferModel(nn.Module):
             body()
         return st['losses'].clone(), st['metrics'].clone()
 
+    def transfer_windows(self, store, batch, donors, score=False, capacity=None):
+        """The inference twin of eval_windows: clip k of the K windows of `batch` (style.data.WindowBatch) of the songs resident
+        in `store` is rendered with the style and the instruments of clip `donors[k]` of the same batch (K ints in [0, K); the
+        identity gives reconstruction), decoded to note records on the device and, with `score`, scored there.  One copy from
+        pinned memory carries the 2 K window descriptors, the K table rows of the clips' songs, the K rows of their donors'
+        songs and the donors (11 K int32).  Then, as one chain on the `clips = K` plan of the batch's shape: two mst_clip_window
+        launches crop the windows (one without percussion) and mst_window_inputs places each clip's own small inputs; the
+        extract stage runs; two mst_clip_gather launches move the `style` vectors — into a bank of K x style_size floats, and
+        back by `donors`; mst_window_inputs places the donors' small inputs (the info and apply stages read the instruments of
+        them); the info and apply stages run; mst_rolls_count / mst_rolls_compact (MST_ROLL_HARD) turn the K predictions of each
+        roll into note records, `capacity` per clip and roll (default min(n_cells, max(4096, n_cells // 8)) of the clip's roll).
+        With `score`, mst_clip_scatter rebuilds from those records the rolls a written file holds (cells without a note are
+        zero, unlike hard_output's dense result, which keeps their durations), mst_roll_metrics compares them with the clips' own
+        notes (note retention), the extract stage runs on them with the donors' small inputs still in place — so the rendered
+        style differs from the donor's through the notes alone — and mst_style_sums leaves the dot products of the rendered, the
+        donor's and the own style (style.metrics.style_cosines).
+
+        From the second use of a plan on, that body replays as one hipGraph per (score, capacity): descriptors, rows and donors
+        are read on the device, so a replay serves other songs, other windows and other donors.  A donor outside [0, K) is not
+        a Python error: the device writes NaNs into that clip's style (and reads no row), and the NaNs show in its predictions.
+        Returns a style.metrics.TransferResult; its note records are on the host, downloaded after ONE synchronising read of
+        the 2 K record counts.  A clip with more records than `capacity` raises MstError naming the capacity it needs: nothing
+        is silently dropped.
+
+        It runs on the current stream, behind whatever train_iteration has enqueued on its lanes (their bookkeeping is left
+        alone), in a workspace, note buffers and descriptors of its own per plan: it touches no gradient buffer, no lane, not
+        the lane counter and not the state of train_windows / eval_windows."""
+        from style.metrics import TransferResult
+        anchor = self._anchor()
+        dev = anchor.device
+        if store.pools[n_pitched_features].cells.device != dev:
+            raise _native.MstError(f'the SongStore lives on {store.device}, the model on {dev}')
+        K, C, R, T, U = batch.K, batch.C, batch.bars, batch.T, batch.percussion
+        donors = np.asarray(donors, dtype=np.int64).reshape(-1)
+        if len(donors) != K:
+            raise ValueError(f'transfer_windows: {len(donors)} donors for a batch of {K} clips')
+        donors = np.clip(donors, -2 ** 31, 2 ** 31 - 1)
+        native = _native.get()
+        plan = self._plan(C, R, T, U, dev, clips=K)
+        bucket = store.buckets[(C, T, U)]
+        names = ('mode', 'bpm', 'instr', 'used_instruments', 'bpm_target')
+        rolls = [(n_pitched_features, 'pitched', C, R * T * n_beat_fractions * n_pitched_notes)]
+        if U:
+            rolls.append((n_unpitched_features, 'unpitched', 1, R * T * n_beat_fractions * n_unpitched_notes))
+        st = plan.__dict__.get('_transfer_window_state')
+        if st is None:
+            n_desc = 2 * K * _native.WINDOW_WORDS
+            roll = lambda *shape: torch.empty((K,) + shape, dtype=torch.float32, device=dev)
+            note_buffers = lambda: dict(pitched=roll(C, R, T, n_beat_fractions, n_pitched_notes, n_pitched_features),
+                                        unpitched=roll(1, R, T, n_beat_fractions, n_unpitched_notes, n_unpitched_features) if U else None)
+            fields = []
+            for name, (a, b) in zip(names, bucket['fields']):
+                off, _, numel = plan.slot(name)
+                if numel != b - a:
+                    raise _native.MstError(f'the store keeps {b - a} floats of {name}, the plan reads {numel}')
+                fields.append((a, b - a, off))
+            style_size = plan.slot('style')[2]
+            st = plan.__dict__['_transfer_window_state'] = dict(
+                ws=plan.new_ws(), notes=note_buffers(), hard=note_buffers(),
+                bank=torch.empty(K, style_size, dtype=torch.float32, device=dev),
+                roll_ws={nfeat: torch.empty(K, native.roll_slices(ch * cells) + 1, dtype=torch.int32, device=dev) for nfeat, _, ch, cells in rolls},
+                records={},                                     # capacity -> per roll (cells, feats), and the 2 K counts
+                style_sums=torch.empty(K, _native.STYLE_SUM_WORDS, dtype=torch.float64, device=dev),
+                retention=torch.zeros(K, C + 1, _native.METRIC_WORDS, dtype=torch.float64, device=dev),
+                metrics={nfeat: (torch.empty(K * ch, _native.METRIC_WORDS, dtype=torch.float64, device=dev),
+                                 torch.empty(native.roll_metrics_scratch_bytes(K * ch, cells) // 8, dtype=torch.float64, device=dev))
+                         for nfeat, _, ch, cells in rolls},
+                # one int32 buffer: the 2 x K window descriptors, the K own table rows, the K donors' table rows, the K donors
+                desc=torch.zeros(n_desc + 3 * K, dtype=torch.int32, device=dev), n_desc=n_desc,
+                # pinned staging slots of that buffer, each reused only after the copy that last read it (its event)
+                stage=[dict(buf=torch.zeros(n_desc + 3 * K, dtype=torch.int32, pin_memory=dev.type == 'cuda'), done=None)
+                       for _ in range(4)],
+                fields=_native.RowFields.of(fields), at=0, graphs={}, uses=0)
+        ws, desc, n_desc = st['ws'], st['desc'], st['n_desc']
+        caps = tuple(min(ch * cells, max(4096, ch * cells // 8) if capacity is None else int(capacity)) for _, _, ch, cells in rolls)
+        if min(caps) < 0:
+            raise ValueError(f'transfer_windows: capacity {capacity}')
+        rec = st['records'].get(caps)
+        if rec is None:
+            rec = st['records'][caps] = dict(counts=torch.empty(2 * K, dtype=torch.int32, device=dev))
+            for (nfeat, _, _, _), cap in zip(rolls, caps):
+                rec[nfeat] = (torch.empty(K, max(cap, 1), dtype=torch.int32, device=dev),
+                              torch.empty(K, max(cap, 1), nfeat, dtype=torch.float32, device=dev))
+        self.join_lanes_keep()
+        stage = st['stage'][st['at'] % len(st['stage'])]
+        st['at'] += 1
+        if stage['done'] is not None and not stage['done'].query():
+            stage['done'].synchronize()
+        host = stage['buf'].numpy()
+        store.describe(batch, host[:n_desc].reshape(2, K, _native.WINDOW_WORDS))
+        own = [store.songs[s]['row'] for s in batch.songs.tolist()]
+        host[n_desc:n_desc + K] = own
+        host[n_desc + K:n_desc + 2 * K] = [own[d] if 0 <= d < K else -1 for d in donors.tolist()]
+        host[n_desc + 2 * K:] = donors
+        desc.copy_(stage['buf'], non_blocking=True)
+        if dev.type == 'cuda':
+            stage['done'] = stage['done'] or torch.cuda.Event()
+            stage['done'].record()
+        pools, table = store.pools, bucket['table']
+        win = desc[:n_desc].view(2, K, _native.WINDOW_WORDS)
+        own_rows, donor_rows, donor_idx = (desc[n_desc + i * K:n_desc + (i + 1) * K] for i in range(3))
+        stream = _native.current_stream
+        style_off, _, style_size = plan.slot('style')
+        style_slots = ws.data_ptr() + 4 * style_off
+
+        def body():
+            notes, hard = st['notes'], st['hard']
+            for nfeat, key, ch, cells in rolls:
+                native.clip_window(pools[nfeat].cells, pools[nfeat].feats, win[0 if key == 'pitched' else 1], notes[key], K, ch, R,
+                                   cells // R, nfeat, stream(dev))
+            # (the table's capacity, not its fill: a capture stays right while songs are added until the table moves)
+            native.window_inputs(table, table.shape[0], table.shape[1], own_rows, K, st['fields'], plan.clip_stride, ws, stream(dev))
+            plan.forward(_native.STAGE_EXTRACT, self._flat, notes['pitched'], notes['unpitched'], ws=ws)
+            # the swap goes through the bank: permuting the slots in place would be a race
+            native.clip_gather(style_slots, K, plan.clip_stride, st['bank'], style_size, None, K, style_size, stream(dev))
+            native.clip_gather(st['bank'], K, style_size, style_slots, plan.clip_stride, donor_idx, K, style_size, stream(dev))
+            native.window_inputs(table, table.shape[0], table.shape[1], donor_rows, K, st['fields'], plan.clip_stride, ws, stream(dev))
+            plan.forward(_native.STAGE_INFO | _native.STAGE_APPLY, self._flat, None, None, ws=ws)
+            for i, ((nfeat, key, ch, cells), cap) in enumerate(zip(rolls, caps)):
+                x = ws.data_ptr() + 4 * plan.slot(key + '_pred')[0]
+                out_cells, out_feats = rec[nfeat]
+                counts = rec['counts'][i * K:(i + 1) * K]
+                native.rolls_count(x, plan.clip_stride, K, ch * cells, nfeat, _native.ROLL_HARD, st['roll_ws'][nfeat], stream(dev))
+                native.rolls_compact(x, plan.clip_stride, K, ch * cells, nfeat, _native.ROLL_HARD, st['roll_ws'][nfeat], cap, out_cells,
+                                     out_feats, counts, stream(dev))
+                if score:
+                    native.clip_scatter(out_cells, out_feats, counts, hard[key], ch * cells, nfeat, n_clips=K, capacity=cap, stream=stream(dev))
+                    records, scratch = st['metrics'][nfeat]
+                    native.roll_metrics(hard[key], notes[key], K * ch, cells, nfeat, scratch, records, stream(dev))
+                    at = slice(0, C) if key == 'pitched' else slice(C, C + 1)
+                    st['retention'][:, at].copy_(records.view(K, ch, _native.METRIC_WORDS))
+            if score:
+                plan.forward(_native.STAGE_EXTRACT, self._flat, hard['pitched'], hard['unpitched'], ws=ws)
+                native.style_sums(style_slots, plan.clip_stride, st['bank'], K, style_size, donor_idx, K, style_size, st['style_sums'],
+                                  stream(dev))
+
+        # keyed by every address the capture bakes in — the parameters, the store's pools and the bucket's table (they move when
+        # they grow), the record buffers of this capacity — and by what the body does
+        key = (self._flat.data_ptr(), table.data_ptr(), bool(score), caps) + \
+            tuple(t.data_ptr() for p in pools.values() for t in (p.cells, p.feats))
+        g = st['graphs'].get(key)
+        if g is None and st['uses'] >= 1 and dev.type == 'cuda' and getattr(self, 'graph_repeated_shapes', True):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                body()
+            st['graphs'][key] = g                               # (one per key in use: with and without score, per capacity)
+        st['uses'] += 1
+        if g is not None:
+            plan._touch(ws)
+            g.replay()
+        else:
+            body()
+        rows_of = lambda name: torch.as_strided(ws, (K, plan.slot(name)[2]), (plan.clip_stride, 1), plan.slot(name)[0]).clone()
+        result = TransferResult(rows_of('instruments_pred'), rows_of('mode_pred'), rows_of('bpm_pred').reshape(K), None, None,
+                                st['style_sums'].clone() if score else None, st['retention'].clone() if score else None)
+        counts = rec['counts'].cpu().view(2, K)                 # the one synchronising read
+        if not U:
+            counts[1] = 0
+        for i, ((nfeat, key, ch, cells), cap) in enumerate(zip(rolls, caps)):
+            most = int(counts[i].max())
+            if most > cap:
+                raise _native.MstError(f'transfer_windows: a clip has {most} {key} note records, the capacity is {cap}; '
+                                       f'pass capacity={max(int(counts[:len(rolls)].max()), 1)}')
+            out_cells, out_feats = rec[nfeat]
+            host_cells, host_feats = out_cells[:, :most].cpu(), out_feats[:, :most].cpu()
+            shape = (1, ch, R, T, n_beat_fractions, n_pitched_notes if key == 'pitched' else n_unpitched_notes, nfeat)
+            setattr(result, key, [SparseRoll(host_cells[k, :n], host_feats[k, :n], shape, pin=False) for k, n in enumerate(counts[i].tolist())])
+        return result
+
     def eval_accumulator(self):
         """The model's accumulator of evaluation rounds (style.train.evaluate_windows): EVAL_ACC_WORDS float64 on the model's
         device, allocated once, so that the graphs of eval_windows bake in one address."""

@@ -170,3 +170,38 @@ def compact(x, mode='nonzero', pin=None, native=None):
     packed[0] = n
     packed[HEADER + n:HEADER + _cells_words(n)] = 0   # the padding behind the cells
     return SparseRoll.from_packed(packed, shape)
+
+
+def stitch_records(rolls, bars):
+    """The SparseRolls of consecutive `bars`-bar windows of one song, in order -> one SparseRoll of (1, C, n * bars, T, ...):
+    the dense rolls concatenated along the bar axis, from the records.  Pure index arithmetic on the cells: a window's cell
+    (c, r, j) becomes (c, w * bars + r, j) of the song; the result is sorted by cell like every SparseRoll."""
+    rolls, bars = list(rolls), int(bars)
+    if not rolls:
+        raise ValueError('stitch_records: no windows')
+    shape = tuple(rolls[0].shape)
+    if len(shape) < 4 or shape[0] != 1 or shape[2] != bars or any(tuple(r.shape) != shape for r in rolls):
+        raise ValueError(f'stitch_records: every window is a roll of (1, C, {bars}, T, ...), got {[tuple(r.shape) for r in rolls]}')
+    per_bar = int(np.prod(shape[3:-1], dtype=np.int64))
+    window, total = bars * per_bar, len(rolls) * bars * per_bar             # cells of one channel: in a window, in the song
+    cells = []
+    for w, roll in enumerate(rolls):
+        c = roll.cells.numpy().astype(np.int64)
+        cells.append(c // window * total + w * window + c % window)
+    cells = np.concatenate(cells)
+    order = np.argsort(cells, kind='stable')
+    feats = np.concatenate([roll.feats.numpy() for roll in rolls])[order]
+    return SparseRoll(cells[order].astype(np.int32), feats, shape[:2] + (len(rolls) * bars,) + shape[3:], pin=False)
+
+
+def crop_bars(roll, n_bars):
+    """The first `n_bars` bars of a SparseRoll of (1, C, R, T, ...): x[:, :, :n_bars] of the dense roll, from the records."""
+    shape, n_bars = tuple(roll.shape), int(n_bars)
+    if len(shape) < 4 or shape[0] != 1 or not 1 <= n_bars <= shape[2]:
+        raise ValueError(f'crop_bars: {n_bars} bars of a roll of {shape}')
+    per_bar = int(np.prod(shape[3:-1], dtype=np.int64))
+    c = roll.cells.numpy().astype(np.int64)
+    channel, rest = c // (shape[2] * per_bar), c % (shape[2] * per_bar)
+    keep = rest < n_bars * per_bar
+    cells = channel[keep] * (n_bars * per_bar) + rest[keep]
+    return SparseRoll(cells.astype(np.int32), roll.feats.numpy()[keep], shape[:2] + (n_bars,) + shape[3:], pin=False)

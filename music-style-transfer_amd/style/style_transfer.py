@@ -53,6 +53,75 @@ def transfer_style(model, composition_path, style_paths, output_path, sparse_out
                     os.path.join(output_path, f'{composition_name} ({style_name} style).mid'), sparse_output=sparse_output)
 
 
+def transfer_songs(model, composition_path, style_paths, output_path, bars=16, K=8, score=False):
+    """`transfer_style` on resident songs, K windows per pass (StyleTransferModel.transfer_windows): the composition and the
+    style songs are loaded as `transfer_style` loads them, kept in a SongStore on the model's device, and for every style song
+    the composition's consecutive `bars`-bar windows (the last one zero-extended) are rendered with the style and the
+    instruments of the style song's window at bar 0.  A batch holds K - 1 composition windows and that donor window, which
+    every donor index points at; the last batch repeats its last window, and the repeats are ignored.  The windows' note
+    records are stitched, cut to the composition's bars and written with `decode_records` as
+    '{composition} ({style} style).mid' — and, rendered with each window's own style, '{composition} (reconstructed).mid' —
+    under output_path/{composition}, with the donor's programs (`channel_slots`), the tempo
+    smf.bpm2tempo(round(mean of bpm_pred over the windows)) and the mode of the largest summed mode_pred, as `apply_style`
+    derives both for one clip.  Unlike `apply_style` the instruments are the donor's own, not the top picks of
+    instruments_pred.  A style song of another (channels, beats per bar, percussion) bucket than the composition's cannot share
+    its batched plan: ValueError naming both (`transfer_style` remains for those).
+
+    With `score` it returns {style name: dict(cosines=the mean over the windows of style.metrics.style_cosines — rendered
+    against donor, rendered against own, own against donor —, pitched=, unpitched= the summed note-retention NoteMetrics)},
+    the reconstruction under the key None; else None."""
+    from style.data import SongStore, WindowBatch, prepare_input_sparse
+    from style.metrics import NoteMetrics, style_cosines
+    from style.sparse import crop_bars, stitch_records
+    bars, K = int(bars), int(K)
+    if bars < 1 or K < 2:
+        raise ValueError('transfer_songs: bars >= 1, and K >= 2 (a batch holds the donor window and at least one other)')
+    name_of = lambda path: os.path.splitext(os.path.basename(path))[0]
+    composition_name = name_of(composition_path)
+    store = SongStore(next(model.parameters()).device)
+    jobs = []
+    for path in [composition_path] + list(style_paths):
+        song_input = get_model_input(path)
+        _, (info, _, _, instruments, _) = song_input
+        song = store.add(prepare_input_sparse(song_input))
+        if store.bucket_of(song) != store.bucket_of(0):
+            raise ValueError(f'{name_of(path)} is of the (channels, beats per bar, percussion) bucket {store.bucket_of(song)}, '
+                             f'{composition_name} of {store.bucket_of(0)}: they cannot share a batch; use transfer_style')
+        jobs.append((song, info, instruments, None if song == 0 else name_of(path)))
+    composition_info = jobs[0][1]
+    C, T, U = store.bucket_of(0)
+    R = store.songs[0]['R']
+    starts = list(range(0, R, bars))
+    output_path = os.path.join(output_path, composition_name)
+    os.makedirs(output_path, exist_ok=True)
+    scores = {}
+    for song, song_info, instruments, style_name in jobs:
+        got = []
+        for at in range(0, len(starts), K - 1):
+            part = starts[at:at + K - 1]
+            live = len(part)
+            part = part + [part[-1]] * (K - 1 - live)
+            batch = WindowBatch(C, bars, T, U, [0] * (K - 1) + [song], part + [0])
+            got.append((model.transfer_windows(store, batch, list(range(K)) if song == 0 else [K - 1] * K, score=score), live))
+        each = lambda pick: [x for res, live in got for x in pick(res)[:live]]
+        bpm = np.asarray(each(lambda res: res.bpm_pred.cpu().tolist()), dtype=np.float64)
+        mode = np.asarray(each(lambda res: res.mode_pred.cpu().tolist()), dtype=np.float64).sum(0)
+        info = dict(composition_info) if song == 0 else combine_info(style_info=song_info, melody_info=composition_info)
+        info['tempo'] = smf.bpm2tempo(round(float(bpm.mean())))
+        info['scale'] = dict(info['scale'], mode=major_mode if int(mode.argmax()) == 0 else minor_mode)
+        pitched = crop_bars(stitch_records(each(lambda res: res.pitched), bars), R)
+        unpitched = crop_bars(stitch_records(each(lambda res: res.unpitched), bars), R) if U else None
+        channels_info, unpitched_info = channel_slots(instruments)
+        mid = decode_records(ChannelConverter(info), channels_info[:C], pitched, unpitched_info if U else None, unpitched)
+        mid.save(os.path.join(output_path, f'{composition_name} (reconstructed).mid' if song == 0 else
+                              f'{composition_name} ({style_name} style).mid'))
+        if score:
+            retention = torch.cat([res.retention[:live] for res, live in got]).cpu()
+            scores[style_name] = dict(cosines=np.concatenate([style_cosines(res.style_sums)[:live] for res, live in got]).mean(0),
+                                      pitched=NoteMetrics(retention[:, :-1]).sum(), unpitched=NoteMetrics(retention[:, -1]).sum())
+    return scores if score else None
+
+
 def get_model_input(path):
     mid = load_midi_from_file(path)
     if mid is None:

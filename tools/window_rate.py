@@ -12,9 +12,14 @@ and their spread).
                windows (windows per second, for every K of --clips; --eval-stride sets the windows' stride), beside it
                style.train.evaluate on the same songs, one song per call (songs per second), and, under device events, the
                two launches a windowed round adds: mst_window_inputs and mst_eval_accumulate at 64 clips.
+  --transfer   times batched style transfer instead of training: StyleTransferModel.transfer_windows for every K of --clips,
+               with and without score (windows per second, --iters windows per timed stretch), interleaved with the per-window
+               Python surface doing the same work (extract_style, predict_song_info, apply_style, hard_output_sparse), and,
+               under device events, the calls it adds at 64 clips: mst_clip_gather, mst_rolls_count, mst_rolls_compact and
+               mst_style_sums.  The model's velocity biases are moved first so that 2 % of the cells are notes.
 One JSON line per measurement; --out writes them all to a file.
 Usage on the GPU box: python tools/window_rate.py [--songs 16] [--iters 150] [--runs 5] [--one-clip] [--kernels] [--eval
-                      [--eval-stride S]] [--out FILE]"""
+                      [--eval-stride S]] [--transfer] [--out FILE]"""
 import argparse
 import json
 import os
@@ -218,6 +223,129 @@ def eval_kernels(model, store, K, reps=50):
     return res
 
 
+def thin_predictions(model, windows, density=.02):
+    """A randomly initialised model predicts every velocity near .5: every cell a note, which no trained model does.  Scale the
+    two appliers' last Linear by 20 and move their velocity bias so that `density` of the cells of `windows`, each rendered in
+    another's style, pass hard_output's .01 threshold — the density of the songs themselves — so that the record buffers and the
+    download are about those of real use.  (The density of a single clip still varies with its donor: TRANSFER_CAPACITY.)"""
+    lift = np.log(.01 / .99)
+    with torch.no_grad():
+        for applier in (model.pitched_style_applier, model.unpitched_style_applier):
+            applier.linear.weight *= 20.
+        styles = [model.extract_style(*w)[0] for w in windows]
+        logits = ([], [])
+        for i, w in enumerate(windows):
+            d = (i * 5 + 3) % len(windows)
+            _, melody, rhythm = model.extract_style(*w)
+            for x, into in zip(model.apply_style(styles[d], melody, rhythm, windows[d][3], True), logits):
+                v = x[..., 1].double().clamp(1e-30, 1 - 1e-16).reshape(-1)
+                into.append(torch.log(v / (1 - v)).float())
+        for applier, rows in zip((model.pitched_style_applier, model.unpitched_style_applier), logits):
+            applier.linear.bias[1] += float(lift - torch.quantile(torch.cat(rows), 1 - density))
+    model._sync_flat()
+
+
+TRANSFER_CAPACITY = C * BARS * T * 560 // 4     # records per clip and roll the --transfer legs leave room for
+
+
+def transfer_legs(model, store, songs, clips, iters, runs):
+    """Windows per second of StyleTransferModel.transfer_windows (every K of `clips`, with and without score; random windows and
+    random donors; each call ends in its one synchronising read and the download of the records) against the per-window Python
+    surface on device-resident dense windows of the same songs — extract_style, predict_song_info with a donor's style,
+    apply_style with the donor's instruments, hard_output_sparse x 2: the only way to do this work before transfer_windows.
+    All legs are warmed up, then timed in turn `runs` times (host clock around a window that ends synchronised)."""
+    from style.data import prepare_input
+    from style.model import hard_output_sparse
+    rng = np.random.default_rng(0)
+    windows = []
+    for name, (info, p, f, ins, u) in songs[:8]:
+        r0 = int(rng.integers(0, p.shape[1] - BARS + 1))
+        windows.append(prepare_input((name, (info, p[:, r0:r0 + BARS], f, ins, u[:, r0:r0 + BARS]))))
+    thin_predictions(model, windows)
+
+    def batched(K, score):
+        def run(n):
+            for _ in range(n):
+                res = model.transfer_windows(store, store.sample(rng, K, BARS), rng.integers(0, K, K), score=score, capacity=TRANSFER_CAPACITY)
+            return K * n, res
+        return run
+
+    styles = []
+
+    def surface(n):
+        with torch.no_grad():
+            if not styles:
+                styles.extend(model.extract_style(*w)[0] for w in windows)
+            for i in range(n):
+                w, d = windows[i % len(windows)], (i * 5 + 3) % len(windows)
+                _, melody, rhythm = model.extract_style(*w)
+                model.predict_song_info(styles[d], rhythm)
+                xp, xu = model.apply_style(styles[d], melody, rhythm, windows[d][3], True)
+                res = hard_output_sparse(xp), hard_output_sparse(xu)
+        return n, res
+    legs = [(f'transfer_windows, K = {K}' + (', score' if score else ''), batched(K, score), max(iters // K, 4)) for K in clips
+            for score in (False, True)]
+    legs.append(('extract_style / predict_song_info / apply_style / hard_output_sparse per window', surface, iters))
+    rates = {name: [] for name, _, _ in legs}
+    records = {}
+    for name, run, n in legs:                              # eager, capture + replay, replays; the plans of every shape
+        _, res = run(3)
+        torch.cuda.synchronize()
+        rolls = res.pitched + res.unpitched if hasattr(res, 'pitched') else list(res)
+        records[name] = sum(r.count for r in rolls) / (len(rolls) / 2)
+    for _ in range(runs):
+        for name, run, n in legs:                          # interleaved
+            t0 = time.perf_counter()
+            done, _ = run(n)
+            torch.cuda.synchronize()
+            rates[name].append(done / (time.perf_counter() - t0))
+    model.check_device_status()
+    return [dict(what=name, bars=BARS, C=C, T=T, records_per_window=records[name], unit='windows/s', **spread(rates[name]))
+            for name, _, _ in legs]
+
+
+def transfer_kernels(model, store, K, reps=50):
+    """Microseconds, under device events, of the calls transfer_windows adds to the existing ones, at K clips: mst_clip_gather of
+    the style vectors (one launch), mst_rolls_count (two launches) and mst_rolls_compact (one) on the K pitched predictions of
+    a batched plan's workspace, and mst_style_sums (one launch)."""
+    from style import _native
+    native, dev = _native.get(), model._anchor().device     # (the device the model keys its plans by)
+    plan = model._plan(C, BARS, T, True, dev, clips=K)
+    model.transfer_windows(store, store.sample(np.random.default_rng(2), K, BARS), list(range(K)),
+                           capacity=TRANSFER_CAPACITY)                                                  # fills a workspace
+    st = plan.__dict__['_transfer_window_state']
+    ws, bank = st['ws'], st['bank']
+    style_off, _, size = plan.slot('style')
+    slots = ws.data_ptr() + 4 * style_off
+    idx = torch.tensor([(k * 5 + 3) % K for k in range(K)], dtype=torch.int32, device=dev)
+    n_cells = C * BARS * T * 560
+    x = ws.data_ptr() + 4 * plan.slot('pitched_pred')[0]
+    rws = torch.empty(K, native.roll_slices(n_cells) + 1, dtype=torch.int32, device=dev)
+    cap = TRANSFER_CAPACITY
+    cells, feats = torch.empty(K, cap, dtype=torch.int32, device=dev), torch.empty(K, cap, 5, device=dev)
+    counts = torch.empty(K, dtype=torch.int32, device=dev)
+    sums = torch.empty(K, _native.STYLE_SUM_WORDS, dtype=torch.float64, device=dev)
+    stream = _native.current_stream(dev)
+    calls = (('mst_clip_gather', lambda: native.clip_gather(bank, K, size, slots, plan.clip_stride, idx, K, size, stream)),
+             ('mst_rolls_count (2 launches)', lambda: native.rolls_count(x, plan.clip_stride, K, n_cells, 5, 1, rws, stream)),
+             ('mst_rolls_compact', lambda: native.rolls_compact(x, plan.clip_stride, K, n_cells, 5, 1, rws, cap, cells, feats, counts, stream)),
+             ('mst_style_sums', lambda: native.style_sums(slots, plan.clip_stride, bank, K, size, idx, K, size, sums, stream)))
+    res = []
+    for name, fn in calls + calls:                         # alternated
+        fn()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            times.append(a.elapsed_time(b) * 1e3)
+        res.append(dict(what=name, K=K, C=C, style_size=size, roll_cells=n_cells, unit='us', **spread(times)))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--songs', type=int, default=16)
@@ -228,6 +356,7 @@ def main():
     ap.add_argument('--kernels', action='store_true')
     ap.add_argument('--eval', action='store_true')
     ap.add_argument('--eval-stride', type=int, default=None)
+    ap.add_argument('--transfer', action='store_true')
     ap.add_argument('--out')
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -245,9 +374,12 @@ def main():
             results.append(eval_rounds(model, store, K, args.eval_stride, args.runs))
         results.append(eval_per_song(model, songs, args.runs))
         results += eval_kernels(model, store, 64)
+    if args.transfer:
+        results += transfer_legs(model, store, songs, args.clips, args.iters, args.runs)
+        results += transfer_kernels(model, store, 64)
     opt = FusedAdam(model)
     opt.zero_grad()
-    for K in [] if args.eval else args.clips:
+    for K in [] if args.eval or args.transfer else args.clips:
         results.append(windowed(model, opt, store, K, args.iters, args.runs))
     if args.one_clip:
         results.append(one_clip(build_model(seed=108), songs, args.iters * 16, args.runs))
