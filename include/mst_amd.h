@@ -453,6 +453,71 @@ int32_t mst_style_sums(const float* a, int64_t a_stride, const float* b, int32_t
                        const int32_t* idx /* DEVICE int32[n_clips] or NULL = identity */, int32_t n_clips, int64_t len,
                        double* out /* n_clips x MST_STYLE_SUM_WORDS, 8-byte aligned */, mst_stream stream);
 
+/* ---- style bank: a clip rendered with a stored style, a blend of stored styles or the style of a song of another shape, and
+ * with the instruments, mode and tempo the model predicts for it, without leaving the device.  The reference's counterpart of
+ * mst_info_decide is the host half of apply_style (style/style_transfer.py:101-116); a bank has none.  Each entry point is one
+ * launch, enqueue-only on `stream` (no allocation, no host synchronisation, capturable as a single chain), without atomics and
+ * without a workgroup waiting for another: the same bits on every run.  Every index array is DEVICE memory, read on the device:
+ * a captured launch serves other rows.
+ *
+ * mst_style_put: per-clip runs of `src` into rows of a bank (bank_rows runs of len floats, bank_stride floats apart).  For clip
+ * k < n_clips with 0 <= rows[k] < bank_rows and i < len:
+ *     bank[rows[k] * bank_stride + i] = src[k * src_stride + i]          copied bit for bit
+ * A rows[k] outside [0, bank_rows) writes nothing for that clip: that is how the repeated windows of a padded batch are dropped.
+ * Every named float is written exactly once and nothing else is written — unless two clips name the same row: which of them the
+ * row then holds is not defined, and keeping the rows distinct is the caller's business.  src is read only; float alignment only.
+ * MST_ERR_ARG, and nothing is launched: a null src, bank or rows; n_clips, bank_rows or len < 1; a negative stride; bank_stride
+ * < len with bank_rows > 1 (the rows would overlap); the ranges [src, src + (n_clips - 1) * src_stride + len) and [bank, bank +
+ * (bank_rows - 1) * bank_stride + len) intersecting or not representable; a pointer not 4-byte aligned; more than 2^31 - 1
+ * chunks of 1024 floats in all. */
+int32_t mst_style_put(const float* src, int64_t src_stride, float* bank, int32_t bank_rows, int64_t bank_stride,
+                      const int32_t* rows /* DEVICE int32[n_clips] */, int32_t n_clips, int64_t len, mst_stream stream);
+
+/* mst_style_mix: a CSR-weighted sum of bank rows into per-clip destinations.  Clip k owns the entries e = offsets[k] ...
+ * offsets[k + 1] - 1 of idx and w (n_entries each; offsets holds n_clips + 1 int32); with x[e] = bank + idx[e] * bank_stride,
+ *     dst[k * dst_stride + i] = (((w[e0] * x[e0][i]) + w[e0 + 1] * x[e0 + 1][i]) + ...)          for i < len
+ * where every product and every sum is rounded to fp32 on its own, left to right, and the first product is not added to a zero:
+ * the bits of a host loop of float32 products and sums in entry order.  So one entry of weight 1.0f copies a row bit for bit
+ * (a NaN's payload aside).  A row may be named more than once.  A clip whose entry range is empty, whose offsets lie outside
+ * [0, n_entries] or decrease, or one of whose idx[e] lies outside [0, bank_rows) gets quiet NaNs (0x7fc00000) in its len floats
+ * instead, and the bank is never read outside its rows.  Every named float of dst is written exactly once and nothing else is
+ * written; the bank, offsets, idx and w are read only.  Rows that start on 16-byte boundaries (bank 16-byte aligned, bank_stride
+ * a multiple of 4) are read 16 bytes at a time, others float by float: the same bits.
+ * MST_ERR_ARG, and nothing is launched: a null pointer; n_clips, bank_rows, n_entries or len < 1; a negative stride; dst_stride
+ * < len with n_clips > 1; the ranges of the bank's rows and of the destinations intersecting or not representable; a pointer
+ * not 4-byte aligned; more than 2^31 - 1 chunks of 1024 floats in all. */
+int32_t mst_style_mix(const float* bank, int32_t bank_rows, int64_t bank_stride,
+                      const int32_t* offsets /* DEVICE int32[n_clips + 1] */, const int32_t* idx /* DEVICE int32[n_entries] */,
+                      const float* w /* DEVICE float[n_entries] */, int32_t n_entries, float* dst, int64_t dst_stride,
+                      int32_t n_clips, int64_t len, mst_stream stream);
+
+/* mst_info_decide: apply_style's decisions, per clip, from the predictions of the info stage.  Clip k's predictions are the
+ * n_logits floats at instruments_pred + k * pred_stride, the 2 at mode_pred + k * pred_stride and the 1 at bpm_pred + k *
+ * pred_stride; its results go to instr / mode / bpm + k * out_stride (a batched plan's slots: both strides are its clip stride).
+ *   ranking  the logits in descending order; equal logits by ascending index; a NaN after every number, NaNs by index.
+ *   picks    percussion is index n_logits - 1; pick c < channels is the c-th entry of the ranking that is not percussion.
+ *   instr    channels rows of (n_logits - 1) + n_groups floats: one_hot(pick c, n_logits - 1) ++ one_hot(group_of[pick c],
+ *            n_groups) — style.data.encode_instruments of the picked programs.  group_of: HOST memory, n_logits - 1 int32 in
+ *            [0, n_groups), read at the call.
+ *   mode     the one-hot (2 floats) of the first index of the larger mode logit (index 0 when they are equal or unordered).
+ *   bpm      rintf(bpm_pred): halves go to even.
+ *   record   decisions[k * (channels + 2) ...]: the picks, percussion's position in the ranking, the mode index.
+ * pool != 0: the logits, the mode logits and bpm_pred are first summed over the clips 0 ... n - 1, each an fp32 left-to-right
+ * sum in clip order that starts from clip 0's value, n = *live clamped to [1, n_clips] (live: one DEVICE int32, NULL = n_clips);
+ * bpm is that sum divided by n.  The one decision is written to every clip, so that all windows of one file play the same
+ * instruments.  Every float of the three results of every clip and every word of decisions is written exactly once and nothing
+ * else is written; the predictions are read only.
+ * MST_ERR_ARG, and nothing is launched: a null pointer (live excepted); n_clips < 1; n_logits outside [2,
+ * MST_DECIDE_MAX_LOGITS]; n_groups outside [1, 127]; channels outside [1, n_logits - 1]; a group_of[i] outside [0, n_groups); a
+ * negative stride; out_stride < channels * (n_logits - 1 + n_groups) with n_clips > 1; a clip's three results intersecting its
+ * predictions or one another; a pointer not 4-byte aligned. */
+#define MST_DECIDE_MAX_LOGITS 64
+int32_t mst_info_decide(const float* instruments_pred, const float* mode_pred, const float* bpm_pred, int64_t pred_stride,
+                        int32_t n_logits, const int32_t* group_of /* HOST, n_logits - 1 */, int32_t n_groups, int32_t channels,
+                        int32_t n_clips, int32_t pool, const int32_t* live /* DEVICE, one int32, or NULL = all */,
+                        float* instr, float* mode, float* bpm, int64_t out_stride,
+                        int32_t* decisions /* n_clips x (channels + 2) */, mst_stream stream);
+
 /* ---- instrumentation (bench.py only; synchronises on HIP events, never used for training):
  * average duration of every launch step of a pass, with its algorithmic FLOPs and bytes.
  * kind: 0 gemm, 1 gather, 2 segment-reduce, 3/4 lstm fwd/bwd, 5/6 combine fwd/bwd, 7/8 melody notes, 9/10 applier notes,

@@ -1707,3 +1707,229 @@ extern "C" int32_t mst_style_sums(const float* a, int64_t a_stride, const float*
                        idx, len, out);
     return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
 }
+
+// ------------------------------------------------------------------ style bank (mst_style_put, mst_style_mix, mst_info_decide)
+// The three small launches that let a style come from a bank of stored rows instead of another clip of the batch: a scatter of
+// the batch's style slots into bank rows, a CSR-weighted sum of bank rows into the slots, and apply_style's host decisions (the
+// top instruments, the mode, the tempo) taken where the predictions lie.  Like their neighbours they are latency-bound and owe
+// exactness: a bit copy, one fixed order of separately rounded fp32 operations, one fixed ranking.
+
+// workgroup b: chunk b % chunks of clip b / chunks, as clip_gather_kernel; a clip whose row is outside the bank writes nothing
+__global__ __launch_bounds__(CG_THREADS) void style_put_kernel(const uint32_t* src, int64_t src_stride, uint32_t* bank, int bank_rows,
+                                                               int64_t bank_stride, const int32_t* rows, int chunks, int64_t len) {
+    const int k = blockIdx.x / chunks;
+    const int row = MST_UNIFORM(rows[k]);
+    if (row < 0 || row >= bank_rows) return;                    // (workgroup-uniform) how a padded batch's repeats are dropped
+    const int64_t c0 = (int64_t)(blockIdx.x % chunks) * CG_CHUNK;
+    const int64_t c1 = c0 + CG_CHUNK < len ? c0 + CG_CHUNK : len;
+    const uint32_t* from = src + (int64_t)k * src_stride;
+    uint32_t* to = bank + (int64_t)row * bank_stride;
+    for (int64_t i = c0 + threadIdx.x; i < c1; i += CG_THREADS) to[i] = from[i];
+}
+
+// do [a, a + 4 * na) and [b, b + 4 * nb) intersect?
+static bool floats_intersect(const void* a, int64_t na, const void* b, int64_t nb) {
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + 4 * (uintptr_t)na, b0 = (uintptr_t)b, b1 = b0 + 4 * (uintptr_t)nb;
+    return a0 < b1 && b0 < a1;
+}
+
+extern "C" int32_t mst_style_put(const float* src, int64_t src_stride, float* bank, int32_t bank_rows, int64_t bank_stride,
+                                 const int32_t* rows, int32_t n_clips, int64_t len, mst_stream stream) {
+    if (!src || !bank || !rows || n_clips < 1 || bank_rows < 1 || len < 1 || src_stride < 0 || bank_stride < 0 ||
+        (bank_stride < len && bank_rows > 1) || ((uintptr_t)src & 3) || ((uintptr_t)bank & 3) || ((uintptr_t)rows & 3))
+        return MST_ERR_ARG;
+    int64_t src_span, bank_span;
+    if (!span_floats(n_clips, src_stride, len, &src_span) || !span_floats(bank_rows, bank_stride, len, &bank_span)) return MST_ERR_ARG;
+    if (floats_intersect(src, src_span, bank, bank_span)) return MST_ERR_ARG;
+    const int64_t chunks = (len + CG_CHUNK - 1) / CG_CHUNK;
+    if (chunks * n_clips > 0x7fffffff) return MST_ERR_ARG;
+    hipLaunchKernelGGL(style_put_kernel, dim3((unsigned)(chunks * n_clips)), dim3(CG_THREADS), 0, (hipStream_t)stream,
+                       (const uint32_t*)src, src_stride, (uint32_t*)bank, (int)bank_rows, bank_stride, rows, (int)chunks, len);
+    return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
+}
+
+// Workgroup b: chunk b % chunks (SM_CHUNK floats) of clip b / chunks; lane t owns floats [4 t, 4 t + 4) of the chunk and walks
+// the clip's entries in order, so a float's chain is ((w0 x0) + w1 x1) + ... with every product and every sum rounded on its own
+// (mul_rounded; the sum of an opaque product cannot contract).  The entries (idx, w) are staged through LDS SM_STAGE at a time
+// with consecutive loads: the row loads then depend on LDS, not on a global load before them.  VEC: every row starts on a 16-byte
+// boundary (bank and bank_stride say so), so a lane's four floats are one load; the ragged tail of a row and the unaligned case
+// take scalar loads.  Only floats of named rows are read.  All loop bounds are workgroup-uniform.
+#define SM_THREADS 256
+#define SM_CHUNK (4 * SM_THREADS)
+#define SM_STAGE 256
+
+template <bool VEC>
+__global__ __launch_bounds__(SM_THREADS) void style_mix_kernel(const float* bank, int bank_rows, int64_t bank_stride, const int32_t* offsets,
+                                                               const int32_t* idx, const float* w, int n_entries, float* dst,
+                                                               int64_t dst_stride, int chunks, int64_t len) {
+    __shared__ int32_t s_idx[SM_STAGE];
+    __shared__ float s_w[SM_STAGE];
+    const int k = blockIdx.x / chunks, tid = threadIdx.x;
+    const int64_t i0 = (int64_t)(blockIdx.x % chunks) * SM_CHUNK + 4 * tid;
+    const int n = (int)(len - i0 >= 4 ? 4 : len - i0 > 0 ? len - i0 : 0);          // floats this lane owns
+    const int e0 = MST_UNIFORM(offsets[k]), e1 = MST_UNIFORM(offsets[k + 1]);
+    bool bad = e0 < 0 || e1 > n_entries || e1 <= e0;            // an empty, decreasing or outlying range: nothing is read
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    const MST_GLOBAL_AS float* bg = (const MST_GLOBAL_AS float*)bank;
+    if (!bad) {
+        for (int s0 = e0; s0 < e1; s0 += SM_STAGE) {
+            const int m = e1 - s0 < SM_STAGE ? e1 - s0 : SM_STAGE;
+            if (tid < m) {
+                s_idx[tid] = idx[s0 + tid];
+                s_w[tid] = w[s0 + tid];
+            }
+            __syncthreads();
+            for (int j = 0; j < m; ++j) {
+                const int row = s_idx[j];
+                const float wj = s_w[j];
+                const bool ok = row >= 0 && row < bank_rows;    // a row outside the bank is never read: the clip becomes NaN
+                bad |= !ok;
+                const MST_GLOBAL_AS float* x = bg + ((ok ? (int64_t)row * bank_stride : 0) + i0);
+                float v[4] = {0.f, 0.f, 0.f, 0.f};
+                if (VEC && n == 4) {
+                    const roll_f4 q = *reinterpret_cast<const MST_GLOBAL_AS roll_f4*>(x);
+                    v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
+                } else {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c)
+                        if (c < n) v[c] = x[c];
+                }
+                const bool first = s0 == e0 && j == 0;          // the first product is not added to a zero
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const float p = mul_rounded(wj, v[c]);
+                    acc[c] = first ? p : acc[c] + p;
+                }
+            }
+            __syncthreads();                                    // the stage is rewritten by the next stretch
+        }
+    }
+    float* to = dst + (int64_t)k * dst_stride + i0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+        if (c < n) to[c] = bad ? __uint_as_float(0x7fc00000u) : acc[c];
+}
+
+extern "C" int32_t mst_style_mix(const float* bank, int32_t bank_rows, int64_t bank_stride, const int32_t* offsets, const int32_t* idx,
+                                 const float* w, int32_t n_entries, float* dst, int64_t dst_stride, int32_t n_clips, int64_t len,
+                                 mst_stream stream) {
+    if (!bank || !offsets || !idx || !w || !dst || n_clips < 1 || bank_rows < 1 || n_entries < 1 || len < 1 || bank_stride < 0 ||
+        dst_stride < 0 || (dst_stride < len && n_clips > 1) || ((uintptr_t)bank & 3) || ((uintptr_t)dst & 3) || ((uintptr_t)offsets & 3) ||
+        ((uintptr_t)idx & 3) || ((uintptr_t)w & 3))
+        return MST_ERR_ARG;
+    int64_t bank_span, dst_span;
+    if (!span_floats(bank_rows, bank_stride, len, &bank_span) || !span_floats(n_clips, dst_stride, len, &dst_span)) return MST_ERR_ARG;
+    if (floats_intersect(bank, bank_span, dst, dst_span)) return MST_ERR_ARG;
+    const int64_t chunks = (len + SM_CHUNK - 1) / SM_CHUNK;
+    if (chunks * n_clips > 0x7fffffff) return MST_ERR_ARG;
+    const dim3 grid((unsigned)(chunks * n_clips)), block(SM_THREADS);
+    if (!((uintptr_t)bank & 15) && bank_stride % 4 == 0)
+        hipLaunchKernelGGL(style_mix_kernel<true>, grid, block, 0, (hipStream_t)stream, bank, (int)bank_rows, bank_stride, offsets, idx, w,
+                           (int)n_entries, dst, dst_stride, (int)chunks, len);
+    else
+        hipLaunchKernelGGL(style_mix_kernel<false>, grid, block, 0, (hipStream_t)stream, bank, (int)bank_rows, bank_stride, offsets, idx, w,
+                           (int)n_entries, dst, dst_stride, (int)chunks, len);
+    return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
+}
+
+// One 64-lane workgroup (one wave) per clip; lane j < n_logits owns logit j.  The ranking is a counting rank: lane j counts the
+// logits that come before its own — a loop of n_logits comparisons whatever the values — and the order is total (descending;
+// equal values by index; a NaN after every number, NaNs by index), so the ranks are a permutation of 0 .. n_logits - 1.  Pooled:
+// every workgroup first sums the live clips' predictions itself, left to right in clip order (no workgroup waits for another),
+// and all take the one decision.
+struct InfoDecideArgs {
+    int32_t n_logits, n_groups, channels, pool, n_clips;
+    int8_t group_of[MST_DECIDE_MAX_LOGITS];
+};
+
+__global__ __launch_bounds__(64) void info_decide_kernel(const float* logits, const float* mode_pred, const float* bpm_pred,
+                                                         int64_t pred_stride, InfoDecideArgs a, const int32_t* live, float* instr,
+                                                         float* mode, float* bpm, int64_t out_stride, int32_t* decisions) {
+    __shared__ float s_x[64];
+    __shared__ int s_rank[64];
+    __shared__ int s_pick[64];
+    const int k = blockIdx.x, j = threadIdx.x, NL = a.n_logits, P = NL - 1;
+    float x = 0.f, m0, m1, b;
+    if (a.pool) {
+        int n = live ? MST_UNIFORM(live[0]) : a.n_clips;
+        n = n < 1 ? 1 : n > a.n_clips ? a.n_clips : n;
+        m0 = mode_pred[0], m1 = mode_pred[1], b = bpm_pred[0];
+        if (j < NL) x = logits[j];
+        for (int c = 1; c < n; ++c) {                           // (workgroup-uniform)
+            const int64_t at = (int64_t)c * pred_stride;
+            if (j < NL) x = x + logits[at + j];
+            m0 = m0 + mode_pred[at], m1 = m1 + mode_pred[at + 1], b = b + bpm_pred[at];
+        }
+        b = b / (float)n;
+    } else {
+        const int64_t at = (int64_t)k * pred_stride;
+        if (j < NL) x = logits[at + j];
+        m0 = mode_pred[at], m1 = mode_pred[at + 1], b = bpm_pred[at];
+    }
+    s_x[j] = x;
+    __syncthreads();
+    int rank = 0;
+    const bool nan_j = x != x;
+    for (int i = 0; i < NL; ++i) {
+        const float y = s_x[i];
+        const bool nan_i = y != y;
+        const bool before = nan_i ? (nan_j && i < j) : (nan_j || y > x || (y == x && i < j));
+        rank += before ? 1 : 0;
+    }
+    s_rank[j] = rank;
+    __syncthreads();
+    const int perc = s_rank[P];
+    if (j < P) {
+        const int pitched_rank = rank - (perc < rank ? 1 : 0);  // its rank among the pitched instruments
+        if (pitched_rank < a.channels) s_pick[pitched_rank] = j;
+    }
+    __syncthreads();
+    const int row = P + a.n_groups;
+    float* out = instr + (int64_t)k * out_stride;
+    for (int e = j; e < a.channels * row; e += 64) {
+        const int c = e / row, f = e - c * row, pick = s_pick[c];
+        out[e] = (f < P ? f == pick : f - P == (int)a.group_of[pick]) ? 1.f : 0.f;
+    }
+    const int major_or_minor = m1 > m0 ? 1 : 0;                 // the first index of the larger logit
+    int32_t* rec = decisions + (int64_t)k * (a.channels + 2);
+    if (j < a.channels) rec[j] = s_pick[j];
+    if (j == 0) {
+        rec[a.channels] = perc;
+        rec[a.channels + 1] = major_or_minor;
+        mode[(int64_t)k * out_stride] = major_or_minor ? 0.f : 1.f;
+        mode[(int64_t)k * out_stride + 1] = major_or_minor ? 1.f : 0.f;
+        bpm[(int64_t)k * out_stride] = rintf(b);
+    }
+}
+
+extern "C" int32_t mst_info_decide(const float* instruments_pred, const float* mode_pred, const float* bpm_pred, int64_t pred_stride,
+                                   int32_t n_logits, const int32_t* group_of, int32_t n_groups, int32_t channels, int32_t n_clips,
+                                   int32_t pool, const int32_t* live, float* instr, float* mode, float* bpm, int64_t out_stride,
+                                   int32_t* decisions, mst_stream stream) {
+    if (!instruments_pred || !mode_pred || !bpm_pred || !group_of || !instr || !mode || !bpm || !decisions || n_clips < 1 ||
+        n_logits < 2 || n_logits > MST_DECIDE_MAX_LOGITS || n_groups < 1 || n_groups > 127 || channels < 1 || channels > n_logits - 1 ||
+        pred_stride < 0 || out_stride < 0)
+        return MST_ERR_ARG;
+    const void* all[] = {instruments_pred, mode_pred, bpm_pred, instr, mode, bpm, decisions, live};
+    for (const void* p : all)
+        if ((uintptr_t)p & 3) return MST_ERR_ARG;
+    // a clip's three results may not lie on its three predictions or on one another (the runs of clip 0 stand for all: the
+    // strides are shared)
+    const int64_t row = (int64_t)(n_logits - 1 + n_groups) * channels;
+    const void* runs[] = {instr, mode, bpm, instruments_pred, mode_pred, bpm_pred};
+    const int64_t lens[] = {row, 2, 1, n_logits, 2, 1};
+    for (int p = 0; p < 3; ++p)
+        for (int q = p + 1; q < 6; ++q)
+            if (floats_intersect(runs[p], lens[p], runs[q], lens[q])) return MST_ERR_ARG;
+    if (n_clips > 1 && out_stride < row) return MST_ERR_ARG;     // the clips' instrument rows would overlap
+    InfoDecideArgs a;
+    a.n_logits = n_logits, a.n_groups = n_groups, a.channels = channels, a.pool = pool != 0, a.n_clips = n_clips;
+    for (int i = 0; i < MST_DECIDE_MAX_LOGITS; ++i) a.group_of[i] = 0;
+    for (int i = 0; i < n_logits - 1; ++i) {
+        if (group_of[i] < 0 || group_of[i] >= n_groups) return MST_ERR_ARG;
+        a.group_of[i] = (int8_t)group_of[i];
+    }
+    hipLaunchKernelGGL(info_decide_kernel, dim3((unsigned)n_clips), dim3(64), 0, (hipStream_t)stream, instruments_pred, mode_pred, bpm_pred,
+                       pred_stride, a, live, instr, mode, bpm, out_stride, decisions);
+    return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
+}

@@ -141,6 +141,10 @@ _SIGS = {
     'mst_rolls_compact': (C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, _P]),
     'mst_clip_gather': (C.c_int32, [_P, C.c_int32, C.c_int64, _P, C.c_int64, _P, C.c_int32, C.c_int64, _P]),
     'mst_style_sums': (C.c_int32, [_P, C.c_int64, _P, C.c_int32, C.c_int64, _P, C.c_int32, C.c_int64, _P, _P]),
+    'mst_style_put': (C.c_int32, [_P, C.c_int64, _P, C.c_int32, C.c_int64, _P, C.c_int32, C.c_int64, _P]),
+    'mst_style_mix': (C.c_int32, [_P, C.c_int32, C.c_int64, _P, _P, _P, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int64, _P]),
+    'mst_info_decide': (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P,
+                                    C.c_int64, _P, _P]),
     'mst_roll_metrics_scratch_bytes': (C.c_int64, [C.c_int64, C.c_int64]),
     'mst_roll_metrics': (C.c_int32, [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P]),
     'mst_eval_scratch_bytes': (C.c_int64, [_P]),
@@ -285,6 +289,36 @@ class Native:
         addr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()
         check(self.lib.mst_style_sums(addr(a), int(a_stride), addr(b), int(b_rows), int(b_stride), addr(idx), int(n_clips), int(length),
                                       addr(out), stream), 'mst_style_sums')
+
+    def style_put(self, src, src_stride, bank, bank_rows, bank_stride, rows, n_clips, length, stream=None):
+        """mst_style_put: bank[rows[k] * bank_stride + i] = src[k * src_stride + i] for k < n_clips, i < length, bit for bit.
+        `rows` (int32, n_clips) is read on the device; a row outside [0, bank_rows) writes nothing for that clip.  Tensors on one
+        device or raw addresses.  Enqueue-only."""
+        addr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()
+        check(self.lib.mst_style_put(addr(src), int(src_stride), addr(bank), int(bank_rows), int(bank_stride), addr(rows), int(n_clips),
+                                     int(length), stream), 'mst_style_put')
+
+    def style_mix(self, bank, bank_rows, bank_stride, offsets, idx, w, n_entries, dst, dst_stride, n_clips, length, stream=None):
+        """mst_style_mix: dst[k * dst_stride + i] = the left-to-right float32 sum over the clip's entries e = offsets[k] ...
+        offsets[k + 1] - 1 of w[e] * bank[idx[e] * bank_stride + i], every product and sum rounded on its own.  `offsets` (int32,
+        n_clips + 1), `idx` (int32) and `w` (float32, n_entries each) are read on the device; an empty or outlying range or an
+        index outside [0, bank_rows) gives quiet NaNs.  Tensors on one device or raw addresses.  Enqueue-only."""
+        addr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()
+        check(self.lib.mst_style_mix(addr(bank), int(bank_rows), int(bank_stride), addr(offsets), addr(idx), addr(w), int(n_entries),
+                                     addr(dst), int(dst_stride), int(n_clips), int(length), stream), 'mst_style_mix')
+
+    def info_decide(self, instruments_pred, mode_pred, bpm_pred, pred_stride, n_logits, group_of, n_groups, channels, n_clips, pool, live,
+                    instr, mode, bpm, out_stride, decisions, stream=None):
+        """mst_info_decide: per clip the top `channels` pitched instruments of the `n_logits` logits as instrument feature rows
+        (`instr`), the one-hot of the larger mode logit (`mode`), rintf(bpm_pred) (`bpm`) and the int32 record of channels + 2
+        words (`decisions`: the picks, percussion's rank, the mode index).  `group_of`: a host sequence of n_logits - 1 group
+        indices.  `pool`: decide once on the sums over the first `live` clips (one int32 on the device, None = all) and write
+        that decision to every clip.  Tensors on one device or raw addresses.  Enqueue-only."""
+        addr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()
+        groups = group_of if isinstance(group_of, C.Array) else (C.c_int32 * len(group_of))(*[int(g) for g in group_of])
+        check(self.lib.mst_info_decide(addr(instruments_pred), addr(mode_pred), addr(bpm_pred), int(pred_stride), int(n_logits), groups,
+                                       int(n_groups), int(channels), int(n_clips), int(bool(pool)), addr(live), addr(instr), addr(mode),
+                                       addr(bpm), int(out_stride), addr(decisions), stream), 'mst_info_decide')
 
     def roll_metrics_scratch_bytes(self, n_groups, group_cells):
         n = self.lib.mst_roll_metrics_scratch_bytes(int(n_groups), int(group_cells))

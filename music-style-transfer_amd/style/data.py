@@ -4,7 +4,7 @@ one-hot encoding, MIDI file -> model input (`iter_inputs`, `get_input`), `prepar
 device (one H2D copy per tensor).  `prepare_input_sparse` is its counterpart for real songs: the note
 tensors stay on the host as sorted note records (`SparseRoll`, `SparseClip`) and are expanded on the
 device by mst_clip_scatter.  `SongStore` keeps the records of many songs on the device and `WindowBatch` names K equally
-shaped windows of them (mst_clip_window crops them there).  sklearn's OneHotEncoder and pandas are not used: categories are the
+shaped windows of them (mst_clip_window crops them there); `StyleBank` keeps style vectors there.  sklearn's OneHotEncoder and pandas are not used: categories are the
 sorted distinct values, which is what `categories='auto'` produces (style/data.py:23-27).
 """
 import numpy as np
@@ -24,6 +24,9 @@ _group_categories = sorted(set(instrument_groups))
 n_instruments = len(included_instruments) + 1            # also percussion
 instrument_size = len(_group_categories) + len(_instrument_categories)   # 51
 percussion_id = len(included_instruments)
+# per instrument logit (the order of _instrument_categories): the index of its GM family among _group_categories — what
+# mst_info_decide needs to write encode_instruments' rows on the device
+group_of_instrument = [_group_categories.index(program2group[p]) for p in _instrument_categories]
 
 
 class CategoryOneHot:
@@ -432,6 +435,117 @@ class SongStore:
                 views[song] = [row[a:b] for a, b in bucket['fields']]
             out += views[song]
         return out
+
+
+class StyleBank:
+    """Style vectors kept on the device, one row each: `rows` is a float32 tensor of `capacity` x `style_size`, grown by
+    doubling and never during a capture (`_RecordPool`'s rule), of which the first `used` rows are taken.  Per row the host keeps
+    where it came from — `provenance[row] = (song, first bar, bars)` — and per song its rows in the order they were taken
+    (`by_song`).  A song is named by whatever the caller names it with (StyleTransferModel.encode_styles uses the SongStore's
+    ids; a library that outlives the store does better with names); rows of every (channels, beats per bar, percussion) bucket
+    share one bank, because a style vector does not depend on the bucket.
+
+    A style to render with is a list of ENTRIES `(row, weight)`: `row(r)` is one stored style, `song(s)` the mean of a song's
+    windows, `blend([...])` a weighted sum of such, and `StyleBank.mix` packs K of them as the CSR arrays mst_style_mix reads.
+    Weights are float32 and products of them are rounded to float32, the arithmetic of the device."""
+
+    def __init__(self, style_size, device=device, capacity=64):
+        self.style_size, self.device = int(style_size), torch.device(device)
+        if self.style_size < 1 or int(capacity) < 1:
+            raise ValueError('StyleBank: style_size and capacity must be at least 1')
+        self.rows = torch.zeros(int(capacity), self.style_size, dtype=torch.float32, device=self.device)
+        self.used, self.provenance, self.by_song = 0, [], {}
+
+    def __len__(self):
+        return self.used
+
+    @property
+    def capacity(self):
+        return self.rows.shape[0]
+
+    def reserve(self, n):
+        """Make room for `n` more rows (the tensor moves when it grows: never during a capture)."""
+        need = self.used + int(n)
+        if need > self.capacity:
+            _not_while_capturing(self.device)
+            capacity = self.capacity
+            while capacity < need:
+                capacity *= 2
+            rows = self.rows.new_zeros(capacity, self.style_size)
+            rows[:self.used].copy_(self.rows[:self.used])
+            self.rows = rows                              # (the old one is recycled in stream order)
+
+    def take(self, song, r0, bars):
+        """Name the next free row as the style of bars [r0, r0 + bars) of `song`; returns the row for whoever fills it."""
+        self.reserve(1)
+        row, self.used = self.used, self.used + 1
+        self.provenance.append((song, int(r0), int(bars)))
+        self.by_song.setdefault(song, []).append(row)
+        return row
+
+    def add(self, song, r0, bars, style):
+        """Store one style vector given as a tensor or array of style_size floats; returns its row."""
+        style = torch.as_tensor(style, dtype=torch.float32).reshape(-1)
+        if style.numel() != self.style_size:
+            raise ValueError(f'StyleBank.add: a style of {style.numel()} floats, the bank holds rows of {self.style_size}')
+        row = self.take(song, r0, bars)
+        self.rows[row].copy_(style)
+        return row
+
+    def row(self, row):
+        if not 0 <= int(row) < self.used:
+            raise KeyError(f'StyleBank: row {row} of {self.used}')
+        return [(int(row), np.float32(1.))]
+
+    def song(self, song):
+        """The mean of the song's windows: its rows, each with the weight float32(1) / float32(n)."""
+        rows = self.by_song.get(song)
+        if not rows:
+            raise KeyError(f'StyleBank: no rows of song {song!r}')
+        return [(r, np.float32(1.) / np.float32(len(rows))) for r in rows]
+
+    def blend(self, parts):
+        """[(what, weight), ...] -> the concatenated entries, each weight scaled (a float32 product).  `what` is a list of entries
+        (from `row`, `song` or `blend`) or the name of a song; a single row goes in as `bank.row(r)`."""
+        out = []
+        for what, weight in parts:
+            entries = what if isinstance(what, list) else self.song(what)
+            out += [(int(r), np.float32(w) * np.float32(weight)) for r, w in entries]
+        if not out:
+            raise ValueError('StyleBank.blend: nothing to blend')
+        return out
+
+    @staticmethod
+    def mix(styles):
+        """K lists of entries -> the host CSR (offsets int32 (K + 1,), idx int32 (n,), w float32 (n,)) of mst_style_mix."""
+        styles = [list(entries) for entries in styles]
+        offsets = np.zeros(len(styles) + 1, dtype=np.int32)
+        offsets[1:] = np.cumsum([len(entries) for entries in styles])
+        idx = np.asarray([r for entries in styles for r, _ in entries], dtype=np.int32)
+        w = np.asarray([x for entries in styles for _, x in entries], dtype=np.float32)
+        return offsets, idx, w
+
+    def save(self, path):
+        """One .npz of the used rows and their provenance (song names as strings, with a flag for those that were ints), so that
+        a style library outlives a session."""
+        songs = [song for song, _, _ in self.provenance]
+        if any(not isinstance(song, (int, np.integer, str)) for song in songs):
+            raise ValueError('StyleBank.save: songs are named by ints or strings')
+        with open(path, 'wb') as f:              # (np.savez given a name appends '.npz' to it)
+            np.savez_compressed(f, rows=self.rows[:self.used].cpu().numpy(), songs=np.asarray([str(song) for song in songs], dtype=np.str_),
+                                is_int=np.asarray([not isinstance(song, str) for song in songs], dtype=np.bool_),
+                                r0=np.asarray([r0 for _, r0, _ in self.provenance], dtype=np.int64),
+                                bars=np.asarray([bars for _, _, bars in self.provenance], dtype=np.int64))
+
+    @classmethod
+    def load(cls, path, device=device):
+        with np.load(path) as z:
+            rows = z['rows']
+            bank = cls(rows.shape[1], device, capacity=max(len(rows), 1))
+            for song, is_int, r0, bars in zip(z['songs'].tolist(), z['is_int'].tolist(), z['r0'].tolist(), z['bars'].tolist()):
+                bank.take(int(song) if is_int else song, r0, bars)
+            bank.rows[:len(rows)].copy_(torch.from_numpy(rows))
+        return bank
 
 
 def prepare_input_sparse(input, max_n_bars=None, pin=None):

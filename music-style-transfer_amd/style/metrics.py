@@ -165,11 +165,16 @@ class TransferResult:
     (1, 1, R, T, 10, 47, 2); `unpitched` is None without percussion): hard_output's note records of the rendered clips.  With
     score=True `style_sums` (K, 8 float64, mst_style_sums' words) and `retention` (K, C + 1, 8 float64, mst_roll_metrics records
     of the written rolls against the clips' own notes: the C pitched channels, then the unpitched roll — zeros without
-    percussion) are on the device, else None.  Every tensor is the result's own: a later call does not change it."""
+    percussion) are on the device, else None.  transfer_styles adds `instr_features` (K, C, 51: the instrument rows the clips
+    were rendered with) and, where the device decided them, `decisions` (K, C + 2 int32, mst_info_decide's records: the C picked
+    logit indices, percussion's position in the ranking, the mode index), both on the device; transfer_windows leaves them None.
+    Every tensor is the result's own: a later call does not change it."""
 
-    def __init__(self, instruments_pred, mode_pred, bpm_pred, pitched, unpitched, style_sums=None, retention=None):
+    def __init__(self, instruments_pred, mode_pred, bpm_pred, pitched, unpitched, style_sums=None, retention=None, decisions=None,
+                 instr_features=None):
         self.instruments_pred, self.mode_pred, self.bpm_pred = instruments_pred, mode_pred, bpm_pred
         self.pitched, self.unpitched, self.style_sums, self.retention = pitched, unpitched, style_sums, retention
+        self.decisions, self.instr_features = decisions, instr_features
 
     @property
     def cosines(self):

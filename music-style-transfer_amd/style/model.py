@@ -693,16 +693,45 @@ class StyleTransferModel(nn.Module):
         It runs on the current stream, behind whatever train_iteration has enqueued on its lanes (their bookkeeping is left
         alone), in a workspace, note buffers and descriptors of its own per plan: it touches no gradient buffer, no lane, not
         the lane counter and not the state of train_windows / eval_windows."""
+        K = batch.K
+        donors = np.asarray(donors, dtype=np.int64).reshape(-1)
+        if len(donors) != K:
+            raise ValueError(f'transfer_windows: {len(donors)} donors for a batch of {K} clips')
+        donors = np.clip(donors, -2 ** 31, 2 ** 31 - 1)
+
+        def fill(tail, own):                                    # the K donors' table rows, the K donors
+            tail[:K] = [own[d] if 0 <= d < K else -1 for d in donors.tolist()]
+            tail[K:] = donors
+
+        def render(c):
+            donor_rows, donor_idx = c.tail[:K], c.tail[K:]
+            bank = c.st['bank']
+            # the swap goes through the bank: permuting the slots in place would be a race
+            c.native.clip_gather(c.style_slots, K, c.plan.clip_stride, bank, c.style_size, None, K, c.style_size, c.stream())
+            c.native.clip_gather(bank, K, c.style_size, c.style_slots, c.plan.clip_stride, donor_idx, K, c.style_size, c.stream())
+            c.native.window_inputs(c.table, c.table.shape[0], c.table.shape[1], donor_rows, K, c.st['fields'], c.plan.clip_stride, c.ws,
+                                   c.stream())
+            c.plan.forward(_native.STAGE_INFO | _native.STAGE_APPLY, self._flat, None, None, ws=c.ws)
+            return K, donor_idx                                 # mst_style_sums: the bank's rows, and the row of a clip's target
+
+        return self._transfer_pass('transfer_windows', lambda plan: (plan.__dict__, '_transfer_window_state'), store, batch, 2 * K, K,
+                                   fill, render, (), score, capacity)
+
+    def _transfer_pass(self, what, state_of, store, batch, tail, bank_rows, fill, render, key_extra, score, capacity, finish=None,
+                       prepare=None):
+        """The body transfer_windows and transfer_styles share: crops, own small inputs, the extract stage, `render` (whatever
+        puts other styles and instruments in place and runs the info and apply stages; it returns the rows of st['bank'] and the
+        device index of each clip's target row for mst_style_sums), the batched compaction and, with `score`, retention and the
+        second extract; one upload of the descriptors, the own rows and `tail` further int32 that `fill(host tail, own rows)`
+        writes; eager on a state's first use, one hipGraph per (score, capacities, key_extra) after it.  `state_of(plan)` names
+        where the state lives: (a dict, its key)."""
+        from types import SimpleNamespace
         from style.metrics import TransferResult
         anchor = self._anchor()
         dev = anchor.device
         if store.pools[n_pitched_features].cells.device != dev:
             raise _native.MstError(f'the SongStore lives on {store.device}, the model on {dev}')
         K, C, R, T, U = batch.K, batch.C, batch.bars, batch.T, batch.percussion
-        donors = np.asarray(donors, dtype=np.int64).reshape(-1)
-        if len(donors) != K:
-            raise ValueError(f'transfer_windows: {len(donors)} donors for a batch of {K} clips')
-        donors = np.clip(donors, -2 ** 31, 2 ** 31 - 1)
         native = _native.get()
         plan = self._plan(C, R, T, U, dev, clips=K)
         bucket = store.buckets[(C, T, U)]
@@ -710,7 +739,8 @@ class StyleTransferModel(nn.Module):
         rolls = [(n_pitched_features, 'pitched', C, R * T * n_beat_fractions * n_pitched_notes)]
         if U:
             rolls.append((n_unpitched_features, 'unpitched', 1, R * T * n_beat_fractions * n_unpitched_notes))
-        st = plan.__dict__.get('_transfer_window_state')
+        holder, state_key = state_of(plan)
+        st = holder.get(state_key)
         if st is None:
             n_desc = 2 * K * _native.WINDOW_WORDS
             roll = lambda *shape: torch.empty((K,) + shape, dtype=torch.float32, device=dev)
@@ -723,9 +753,9 @@ class StyleTransferModel(nn.Module):
                     raise _native.MstError(f'the store keeps {b - a} floats of {name}, the plan reads {numel}')
                 fields.append((a, b - a, off))
             style_size = plan.slot('style')[2]
-            st = plan.__dict__['_transfer_window_state'] = dict(
+            st = holder[state_key] = dict(
                 ws=plan.new_ws(), notes=note_buffers(), hard=note_buffers(),
-                bank=torch.empty(K, style_size, dtype=torch.float32, device=dev),
+                bank=torch.empty(bank_rows, style_size, dtype=torch.float32, device=dev),
                 roll_ws={nfeat: torch.empty(K, native.roll_slices(ch * cells) + 1, dtype=torch.int32, device=dev) for nfeat, _, ch, cells in rolls},
                 records={},                                     # capacity -> per roll (cells, feats), and the 2 K counts
                 style_sums=torch.empty(K, _native.STYLE_SUM_WORDS, dtype=torch.float64, device=dev),
@@ -733,16 +763,18 @@ class StyleTransferModel(nn.Module):
                 metrics={nfeat: (torch.empty(K * ch, _native.METRIC_WORDS, dtype=torch.float64, device=dev),
                                  torch.empty(native.roll_metrics_scratch_bytes(K * ch, cells) // 8, dtype=torch.float64, device=dev))
                          for nfeat, _, ch, cells in rolls},
-                # one int32 buffer: the 2 x K window descriptors, the K own table rows, the K donors' table rows, the K donors
-                desc=torch.zeros(n_desc + 3 * K, dtype=torch.int32, device=dev), n_desc=n_desc,
+                # one int32 buffer: the 2 x K window descriptors, the K own table rows, the caller's tail
+                desc=torch.zeros(n_desc + K + tail, dtype=torch.int32, device=dev), n_desc=n_desc,
                 # pinned staging slots of that buffer, each reused only after the copy that last read it (its event)
-                stage=[dict(buf=torch.zeros(n_desc + 3 * K, dtype=torch.int32, pin_memory=dev.type == 'cuda'), done=None)
+                stage=[dict(buf=torch.zeros(n_desc + K + tail, dtype=torch.int32, pin_memory=dev.type == 'cuda'), done=None)
                        for _ in range(4)],
                 fields=_native.RowFields.of(fields), at=0, graphs={}, uses=0)
         ws, desc, n_desc = st['ws'], st['desc'], st['n_desc']
+        if prepare is not None:
+            prepare(st, plan)
         caps = tuple(min(ch * cells, max(4096, ch * cells // 8) if capacity is None else int(capacity)) for _, _, ch, cells in rolls)
         if min(caps) < 0:
-            raise ValueError(f'transfer_windows: capacity {capacity}')
+            raise ValueError(f'{what}: capacity {capacity}')
         rec = st['records'].get(caps)
         if rec is None:
             rec = st['records'][caps] = dict(counts=torch.empty(2 * K, dtype=torch.int32, device=dev))
@@ -758,18 +790,19 @@ class StyleTransferModel(nn.Module):
         store.describe(batch, host[:n_desc].reshape(2, K, _native.WINDOW_WORDS))
         own = [store.songs[s]['row'] for s in batch.songs.tolist()]
         host[n_desc:n_desc + K] = own
-        host[n_desc + K:n_desc + 2 * K] = [own[d] if 0 <= d < K else -1 for d in donors.tolist()]
-        host[n_desc + 2 * K:] = donors
+        fill(host[n_desc + K:], own)
         desc.copy_(stage['buf'], non_blocking=True)
         if dev.type == 'cuda':
             stage['done'] = stage['done'] or torch.cuda.Event()
             stage['done'].record()
         pools, table = store.pools, bucket['table']
         win = desc[:n_desc].view(2, K, _native.WINDOW_WORDS)
-        own_rows, donor_rows, donor_idx = (desc[n_desc + i * K:n_desc + (i + 1) * K] for i in range(3))
+        own_rows = desc[n_desc:n_desc + K]
         stream = _native.current_stream
         style_off, _, style_size = plan.slot('style')
         style_slots = ws.data_ptr() + 4 * style_off
+        c = SimpleNamespace(native=native, plan=plan, st=st, ws=ws, tail=desc[n_desc + K:], table=table, style_slots=style_slots,
+                            style_size=style_size, stream=lambda: stream(dev), dev=dev)   # (the stream is read inside a capture too)
 
         def body():
             notes, hard = st['notes'], st['hard']
@@ -779,11 +812,7 @@ class StyleTransferModel(nn.Module):
             # (the table's capacity, not its fill: a capture stays right while songs are added until the table moves)
             native.window_inputs(table, table.shape[0], table.shape[1], own_rows, K, st['fields'], plan.clip_stride, ws, stream(dev))
             plan.forward(_native.STAGE_EXTRACT, self._flat, notes['pitched'], notes['unpitched'], ws=ws)
-            # the swap goes through the bank: permuting the slots in place would be a race
-            native.clip_gather(style_slots, K, plan.clip_stride, st['bank'], style_size, None, K, style_size, stream(dev))
-            native.clip_gather(st['bank'], K, style_size, style_slots, plan.clip_stride, donor_idx, K, style_size, stream(dev))
-            native.window_inputs(table, table.shape[0], table.shape[1], donor_rows, K, st['fields'], plan.clip_stride, ws, stream(dev))
-            plan.forward(_native.STAGE_INFO | _native.STAGE_APPLY, self._flat, None, None, ws=ws)
+            sum_rows, sum_idx = render(c)
             for i, ((nfeat, key, ch, cells), cap) in enumerate(zip(rolls, caps)):
                 x = ws.data_ptr() + 4 * plan.slot(key + '_pred')[0]
                 out_cells, out_feats = rec[nfeat]
@@ -799,12 +828,12 @@ class StyleTransferModel(nn.Module):
                     st['retention'][:, at].copy_(records.view(K, ch, _native.METRIC_WORDS))
             if score:
                 plan.forward(_native.STAGE_EXTRACT, self._flat, hard['pitched'], hard['unpitched'], ws=ws)
-                native.style_sums(style_slots, plan.clip_stride, st['bank'], K, style_size, donor_idx, K, style_size, st['style_sums'],
+                native.style_sums(style_slots, plan.clip_stride, st['bank'], sum_rows, style_size, sum_idx, K, style_size, st['style_sums'],
                                   stream(dev))
 
         # keyed by every address the capture bakes in — the parameters, the store's pools and the bucket's table (they move when
         # they grow), the record buffers of this capacity — and by what the body does
-        key = (self._flat.data_ptr(), table.data_ptr(), bool(score), caps) + \
+        key = (self._flat.data_ptr(), table.data_ptr(), bool(score), caps) + tuple(key_extra) + \
             tuple(t.data_ptr() for p in pools.values() for t in (p.cells, p.feats))
         g = st['graphs'].get(key)
         if g is None and st['uses'] >= 1 and dev.type == 'cuda' and getattr(self, 'graph_repeated_shapes', True):
@@ -821,19 +850,228 @@ class StyleTransferModel(nn.Module):
         rows_of = lambda name: torch.as_strided(ws, (K, plan.slot(name)[2]), (plan.clip_stride, 1), plan.slot(name)[0]).clone()
         result = TransferResult(rows_of('instruments_pred'), rows_of('mode_pred'), rows_of('bpm_pred').reshape(K), None, None,
                                 st['style_sums'].clone() if score else None, st['retention'].clone() if score else None)
+        if finish is not None:
+            finish(c, result, rows_of)
         counts = rec['counts'].cpu().view(2, K)                 # the one synchronising read
         if not U:
             counts[1] = 0
         for i, ((nfeat, key, ch, cells), cap) in enumerate(zip(rolls, caps)):
             most = int(counts[i].max())
             if most > cap:
-                raise _native.MstError(f'transfer_windows: a clip has {most} {key} note records, the capacity is {cap}; '
+                raise _native.MstError(f'{what}: a clip has {most} {key} note records, the capacity is {cap}; '
                                        f'pass capacity={max(int(counts[:len(rolls)].max()), 1)}')
             out_cells, out_feats = rec[nfeat]
             host_cells, host_feats = out_cells[:, :most].cpu(), out_feats[:, :most].cpu()
             shape = (1, ch, R, T, n_beat_fractions, n_pitched_notes if key == 'pitched' else n_unpitched_notes, nfeat)
             setattr(result, key, [SparseRoll(host_cells[k, :n], host_feats[k, :n], shape, pin=False) for k, n in enumerate(counts[i].tolist())])
         return result
+
+    def encode_styles(self, store, bars, K, stride=None, bank=None):
+        """The style of every window of every song resident in `store`, kept on the device: for every batch of
+        `store.window_batches(bars, K, stride)` — bucket by bucket — two mst_clip_window launches crop the windows,
+        mst_window_inputs places the clips' small inputs, the extract stage of the `clips = K` plan runs and mst_style_put
+        scatters the K `style` slots into rows of `bank` (a style.data.StyleBank; None: a new one) by a row list read on the
+        device, -1 for the repeats that pad a bucket's last batch.  Songs of every bucket land in the one bank; the bank's
+        provenance names each row's (song id of the store, first bar, bars).  Per plan the pass has a workspace, note buffers and
+        descriptors of its own (not the lanes', not the other window states'); one copy from pinned memory carries descriptors,
+        table rows and bank rows, and from the second use of a plan on the body replays as one hipGraph.  The rows for all
+        windows are reserved before the first batch, so the bank does not move in between.  Nothing is downloaded.
+        Returns the bank."""
+        from style.data import StyleBank
+        anchor = self._anchor()
+        dev = anchor.device
+        if store.pools[n_pitched_features].cells.device != dev:
+            raise _native.MstError(f'the SongStore lives on {store.device}, the model on {dev}')
+        todo = store.window_batches(bars, K, stride)
+        K = int(K)
+        w = dict(_DEFAULT_WIDTHS)
+        w.update(self._widths)
+        if bank is None:
+            bank = StyleBank(w['style'], dev)
+        if bank.style_size != w['style'] or bank.rows.device != dev:
+            raise _native.MstError(f'encode_styles: a bank of {bank.style_size} floats per row on {bank.rows.device}, the model has '
+                                   f'styles of {w["style"]} on {dev}')
+        bank.reserve(sum(live for _, live in todo))
+        native = _native.get()
+        names = ('mode', 'bpm', 'instr', 'used_instruments', 'bpm_target')
+        stream = _native.current_stream
+        self.join_lanes_keep()
+        for batch, live in todo:
+            C, R, T, U = batch.C, batch.bars, batch.T, batch.percussion
+            plan = self._plan(C, R, T, U, dev, clips=K)
+            bucket = store.buckets[(C, T, U)]
+            st = plan.__dict__.get('_encode_style_state')
+            if st is None:
+                n_desc = 2 * K * _native.WINDOW_WORDS
+                roll = lambda *shape: torch.empty((K,) + shape, dtype=torch.float32, device=dev)
+                fields = []
+                for name, (a, b) in zip(names, bucket['fields']):
+                    off, _, numel = plan.slot(name)
+                    if numel != b - a:
+                        raise _native.MstError(f'the store keeps {b - a} floats of {name}, the plan reads {numel}')
+                    fields.append((a, b - a, off))
+                st = plan.__dict__['_encode_style_state'] = dict(
+                    ws=plan.new_ws(), pitched=roll(C, R, T, n_beat_fractions, n_pitched_notes, n_pitched_features),
+                    unpitched=roll(1, R, T, n_beat_fractions, n_unpitched_notes, n_unpitched_features) if U else None,
+                    # one int32 buffer: the 2 x K window descriptors, the K table rows, the K bank rows
+                    desc=torch.zeros(n_desc + 2 * K, dtype=torch.int32, device=dev), n_desc=n_desc,
+                    stage=[dict(buf=torch.zeros(n_desc + 2 * K, dtype=torch.int32, pin_memory=dev.type == 'cuda'), done=None)
+                           for _ in range(4)],
+                    fields=_native.RowFields.of(fields), at=0, graph=None, key=None, uses=0)
+            ws, desc, n_desc = st['ws'], st['desc'], st['n_desc']
+            stage = st['stage'][st['at'] % len(st['stage'])]
+            st['at'] += 1
+            if stage['done'] is not None and not stage['done'].query():
+                stage['done'].synchronize()
+            host = stage['buf'].numpy()
+            store.describe(batch, host[:n_desc].reshape(2, K, _native.WINDOW_WORDS))
+            host[n_desc:n_desc + K] = [store.songs[s]['row'] for s in batch.songs.tolist()]
+            host[n_desc + K:] = -1
+            for k, (song, r0) in enumerate(zip(batch.songs.tolist()[:live], batch.r0s.tolist()[:live])):
+                host[n_desc + K + k] = bank.take(song, r0, R)
+            desc.copy_(stage['buf'], non_blocking=True)
+            if dev.type == 'cuda':
+                stage['done'] = stage['done'] or torch.cuda.Event()
+                stage['done'].record()
+            pools, table, rows = store.pools, bucket['table'], bank.rows
+            win = desc[:n_desc].view(2, K, _native.WINDOW_WORDS)
+            style_off, _, style_size = plan.slot('style')
+
+            def body():
+                native.clip_window(pools[n_pitched_features].cells, pools[n_pitched_features].feats, win[0], st['pitched'], K, C, R,
+                                   T * n_beat_fractions * n_pitched_notes, n_pitched_features, stream(dev))
+                if U:
+                    native.clip_window(pools[n_unpitched_features].cells, pools[n_unpitched_features].feats, win[1], st['unpitched'],
+                                       K, 1, R, T * n_beat_fractions * n_unpitched_notes, n_unpitched_features, stream(dev))
+                native.window_inputs(table, table.shape[0], table.shape[1], desc[n_desc:n_desc + K], K, st['fields'], plan.clip_stride,
+                                     ws, stream(dev))
+                plan.forward(_native.STAGE_EXTRACT, self._flat, st['pitched'], st['unpitched'], ws=ws)
+                # (the bank's capacity, not its fill: a capture stays right while rows are taken until the bank moves)
+                native.style_put(ws.data_ptr() + 4 * style_off, plan.clip_stride, rows, rows.shape[0], style_size, desc[n_desc + K:], K,
+                                 style_size, stream(dev))
+
+            # keyed by every address the capture bakes in: the parameters, the pools, the table and the bank (they move when they grow)
+            key = (self._flat.data_ptr(), table.data_ptr(), rows.data_ptr(), rows.shape[0]) + \
+                tuple(t.data_ptr() for p in pools.values() for t in (p.cells, p.feats))
+            g = st['graph'] if st['key'] == key else None
+            if g is None and st['uses'] >= 1 and dev.type == 'cuda' and getattr(self, 'graph_repeated_shapes', True):
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    body()
+                st['graph'], st['key'] = g, key
+            st['uses'] += 1
+            if g is not None:
+                plan._touch(ws)
+                g.replay()
+            else:
+                body()
+        return bank
+
+    def transfer_styles(self, store, batch, bank, mix, instruments='each', score=False, capacity=None, live=None):
+        """transfer_windows with styles out of a bank: clip k of the K windows of `batch` is rendered with the weighted sum
+        `mix` names for it of rows of `bank` (a style.data.StyleBank on the model's device) — a stored style, the mean of a
+        song's windows, a blend of songs, a song of another (channels, beats per bar, percussion) bucket: a style vector does
+        not depend on the bucket.  `mix` is StyleBank.mix's CSR (offsets, idx, w) or the K entry lists it is made of.
+        `instruments` says what the clips play: 'each' — per clip the top C pitched instruments of its own instruments_pred,
+        apply_style's rule (style.style_transfer.select_instruments), decided on the device by mst_info_decide together with the
+        mode and the rounded tempo; 'pooled' — one such decision on the predictions summed over the first `live` clips (default
+        all K), written to every clip, so that the windows of one file play the same instruments; or a float tensor of
+        (1, C, 51) or (K, C, 51) instrument feature rows, placed as given (mode and tempo slots then stay the clips' own).
+
+        The chain on the `clips = K` plan: the crops, the clips' own small inputs and the extract stage as in transfer_windows;
+        mst_style_mix from the bank into the `style` slots; the info stage; mst_info_decide, or mst_clip_gather of the given
+        rows into the `instr` slots; the apply stage; mst_rolls_count / mst_rolls_compact.  With `score` the own styles and the
+        mixed targets are kept in one side buffer of 2 K rows, so that mst_style_sums scores the rendered style against target
+        row K + k and own row k; the second extract reads the decided mode, tempo and instruments; note retention is
+        transfer_windows'.  One copy from pinned memory carries the descriptors, the table rows and the CSR.  The CSR has an
+        entry capacity per state (the next power of two, at least 4 K): more entries than a state holds means another state,
+        never a silent cut.  From a state's second use on the body replays as one hipGraph per (score, capacity, instruments
+        kind, entry capacity): rows, offsets, indices, weights and `live` are read on the device, so a replay serves other
+        windows and other mixes.  A clip whose entries are empty or name a row outside the bank gets NaNs for a style, which
+        show in its predictions; rows at or beyond len(bank) but inside its capacity are not checked.
+
+        Returns a style.metrics.TransferResult with `instr_features` (K, C, 51) and, where the device decided, `decisions`
+        (K, C + 2 int32).  What transfer_windows says about streams, lanes and the training state holds here: the states are
+        this method's own."""
+        from style.data import StyleBank, group_of_instrument
+        K, C = batch.K, batch.C
+        dev = self._anchor().device
+        if bank.rows.device != dev:
+            raise _native.MstError(f'the StyleBank lives on {bank.rows.device}, the model on {dev}')
+        offsets, idx, w = mix if isinstance(mix, tuple) and len(mix) == 3 and not isinstance(mix[0], list) else StyleBank.mix(mix)
+        offsets, idx = np.asarray(offsets, dtype=np.int32).reshape(-1), np.asarray(idx, dtype=np.int32).reshape(-1)
+        w = np.ascontiguousarray(np.asarray(w, dtype=np.float32).reshape(-1))
+        if len(offsets) != K + 1 or len(idx) != len(w):
+            raise ValueError(f'transfer_styles: a mix of {len(offsets) - 1} clips and {len(idx)} / {len(w)} entries for a batch of {K}')
+        n_entries = len(idx)
+        entry_cap = 4 * K
+        while entry_cap < n_entries:
+            entry_cap *= 2
+        given = None
+        if torch.is_tensor(instruments):
+            given = instruments.to(dev, torch.float32)
+            kind = 'given'
+            if given.dim() != 3 or given.shape[0] not in (1, K) or given.shape[1] != C:
+                raise ValueError(f'transfer_styles: instruments of {tuple(instruments.shape)}, not (1 or {K}, {C}, instrument features)')
+        elif instruments in ('each', 'pooled'):
+            kind = instruments
+        else:
+            raise ValueError(f"transfer_styles: instruments is 'each', 'pooled' or a tensor, not {instruments!r}")
+        live = K if live is None else int(live)
+        at_off, at_live, at_idx, at_w = K, 2 * K + 1, 2 * K + 2, 2 * K + 2 + entry_cap      # the tail: targets, offsets, live, idx, w
+
+        def fill(tail, own):
+            tail[:K] = np.arange(K, 2 * K)                      # mst_style_sums: clip k's target is row K + k of the side buffer
+            tail[at_off:at_off + K + 1] = offsets
+            tail[at_live] = live
+            tail[at_idx:at_idx + n_entries] = idx
+            tail[at_idx + n_entries:at_w] = -1
+            tail[at_w:at_w + n_entries] = w.view(np.int32)
+            tail[at_w + n_entries:] = 0
+
+        def render(c):
+            plan, ws, native, st = c.plan, c.ws, c.native, c.st
+            side, rows = st['bank'], bank.rows
+            slot = lambda name: ws.data_ptr() + 4 * plan.slot(name)[0]
+            if score:                                           # the own styles: rows [0, K) of the side buffer
+                native.clip_gather(c.style_slots, K, plan.clip_stride, side, c.style_size, None, K, c.style_size, c.stream())
+            # (the bank's capacity, not its fill: a capture stays right while rows are added until the bank moves)
+            native.style_mix(rows, rows.shape[0], c.style_size, c.tail[at_off:], c.tail[at_idx:], c.tail[at_w:].view(torch.float32),
+                             entry_cap, c.style_slots, plan.clip_stride, K, c.style_size, c.stream())
+            if score:                                           # the mixed targets: rows [K, 2 K)
+                native.clip_gather(c.style_slots, K, plan.clip_stride, side[K:], c.style_size, None, K, c.style_size, c.stream())
+            plan.forward(_native.STAGE_INFO, self._flat, None, None, ws=ws)
+            row = plan.slot('instr')[2]
+            if given is None:
+                n_logits = plan.slot('instruments_pred')[2]
+                native.info_decide(slot('instruments_pred'), slot('mode_pred'), slot('bpm_pred'), plan.clip_stride, n_logits,
+                                   group_of_instrument, row // C - (n_logits - 1), C, K, kind == 'pooled', c.tail[at_live:], slot('instr'),
+                                   slot('mode'), slot('bpm'), plan.clip_stride, st['decisions'], c.stream())
+            else:
+                native.clip_gather(st['given'], K, row if given.shape[0] == K else 0, slot('instr'), plan.clip_stride, None, K, row,
+                                   c.stream())
+            plan.forward(_native.STAGE_APPLY, self._flat, None, None, ws=ws)
+            return 2 * K, c.tail[:K]
+
+        def state_of(plan):
+            return plan.__dict__.setdefault('_transfer_style_state', {}), entry_cap
+
+        def prepare(st, plan):                                  # buffers a state of this method owns beside the shared ones
+            if 'decisions' not in st:
+                st['decisions'] = torch.zeros(K, C + 2, dtype=torch.int32, device=dev)
+                st['given'] = torch.zeros(K, plan.slot('instr')[2], dtype=torch.float32, device=dev)
+            if given is not None:
+                if given[0].numel() != plan.slot('instr')[2]:
+                    raise ValueError(f'transfer_styles: instrument rows of {given[0].numel()} floats, the plan reads {plan.slot("instr")[2]}')
+                st['given'][:given.shape[0]].copy_(given.reshape(given.shape[0], -1))
+
+        def finish(c, result, rows_of):
+            result.instr_features = rows_of('instr').view(K, C, -1)
+            result.decisions = c.st['decisions'].clone() if given is None else None
+
+        key_extra = (kind, entry_cap, bank.rows.data_ptr(), bank.rows.shape[0], None if given is None else given.shape[0])
+        return self._transfer_pass('transfer_styles', state_of, store, batch, at_w + entry_cap, 2 * K, fill, render, key_extra, score,
+                                   capacity, finish=finish, prepare=prepare)
 
     def eval_accumulator(self):
         """The model's accumulator of evaluation rounds (style.train.evaluate_windows): EVAL_ACC_WORDS float64 on the model's

@@ -53,7 +53,8 @@ def transfer_style(model, composition_path, style_paths, output_path, sparse_out
                     os.path.join(output_path, f'{composition_name} ({style_name} style).mid'), sparse_output=sparse_output)
 
 
-def transfer_songs(model, composition_path, style_paths, output_path, bars=16, K=8, score=False):
+def transfer_songs(model, composition_path, style_paths, output_path, bars=16, K=8, score=False, song_styles=False, blends=(),
+                   instruments='donor'):
     """`transfer_style` on resident songs, K windows per pass (StyleTransferModel.transfer_windows): the composition and the
     style songs are loaded as `transfer_style` loads them, kept in a SongStore on the model's device, and for every style song
     the composition's consecutive `bars`-bar windows (the last one zero-extended) are rendered with the style and the
@@ -69,13 +70,29 @@ def transfer_songs(model, composition_path, style_paths, output_path, bars=16, K
 
     With `score` it returns {style name: dict(cosines=the mean over the windows of style.metrics.style_cosines — rendered
     against donor, rendered against own, own against donor —, pitched=, unpitched= the summed note-retention NoteMetrics)},
-    the reconstruction under the key None; else None."""
+    the reconstruction under the key None; else None.
+
+    `song_styles`, `blends` and `instruments` lift those limits through a style bank (StyleTransferModel.encode_styles /
+    transfer_styles); with their defaults nothing above changes.  Every song is then encoded once — its full, sounding
+    `bars`-bar windows at stride `bars` (SongStore.windows) — and a batch holds K composition windows.
+    song_styles=True: a style song's style is the mean of its windows instead of its window at bar 0.
+    blends=[{'name': 'half', 'parts': {'first': .5, 'second': .5}}]: besides the style songs' files, '{composition} (half
+    style).mid' rendered with the weighted sum of the named style songs' styles; scale, donor instruments and style name are
+    those of its first part.
+    instruments='predicted': the clips play what the model predicts, not the donor's programs — apply_style's rule, decided on
+    the device (mst_info_decide) once per file, on the predictions summed over the live windows of the file's first batch; the
+    later batches reuse that batch's instrument rows, and the programs written are the decided ones.  The donor's instrument
+    rows are then not needed, so a style song of another bucket than the composition's is accepted."""
     from style.data import SongStore, WindowBatch, prepare_input_sparse
     from style.metrics import NoteMetrics, style_cosines
     from style.sparse import crop_bars, stitch_records
     bars, K = int(bars), int(K)
     if bars < 1 or K < 2:
         raise ValueError('transfer_songs: bars >= 1, and K >= 2 (a batch holds the donor window and at least one other)')
+    play = instruments
+    if play not in ('donor', 'predicted'):
+        raise ValueError(f"transfer_songs: instruments is 'donor' or 'predicted', not {play!r}")
+    through_bank = bool(song_styles) or bool(blends) or play == 'predicted'
     name_of = lambda path: os.path.splitext(os.path.basename(path))[0]
     composition_name = name_of(composition_path)
     store = SongStore(next(model.parameters()).device)
@@ -84,7 +101,7 @@ def transfer_songs(model, composition_path, style_paths, output_path, bars=16, K
         song_input = get_model_input(path)
         _, (info, _, _, instruments, _) = song_input
         song = store.add(prepare_input_sparse(song_input))
-        if store.bucket_of(song) != store.bucket_of(0):
+        if store.bucket_of(song) != store.bucket_of(0) and play != 'predicted':
             raise ValueError(f'{name_of(path)} is of the (channels, beats per bar, percussion) bucket {store.bucket_of(song)}, '
                              f'{composition_name} of {store.bucket_of(0)}: they cannot share a batch; use transfer_style')
         jobs.append((song, info, instruments, None if song == 0 else name_of(path)))
@@ -95,6 +112,42 @@ def transfer_songs(model, composition_path, style_paths, output_path, bars=16, K
     output_path = os.path.join(output_path, composition_name)
     os.makedirs(output_path, exist_ok=True)
     scores = {}
+    if through_bank:
+        bank = model.encode_styles(store, bars, K)
+
+        def style_of(song):
+            rows = bank.by_song.get(song, [])
+            first = [r for r in rows if bank.provenance[r][1] == 0]
+            if not rows or not (song_styles or first):
+                raise ValueError(f'transfer_songs: {jobs[song][3]} has no full, sounding window of {bars} bars to take a style from')
+            return bank.song(song) if song_styles else bank.row(first[0])
+        by_name = {job[3]: job for job in jobs[1:]}
+        todo = [(job, style_of(job[0]), job[3]) for job in jobs[1:]]
+        for blend in blends:
+            parts = list(blend['parts'].items())
+            missing = [name for name, _ in parts if name not in by_name]
+            if missing or not parts:
+                raise ValueError(f'transfer_songs: the blend {blend["name"]!r} names {missing or "no style song"}')
+            todo.append((by_name[parts[0][0]], bank.blend([(style_of(by_name[name][0]), weight) for name, weight in parts]), blend['name']))
+        for (song, song_info, donor_programs, _), entries, style_name in todo:
+            if play == 'donor' and store.bucket_of(song) != store.bucket_of(0):
+                raise ValueError(f'{style_name}: donor instruments need a style song of the bucket {store.bucket_of(0)}')
+            got, rows = [], None
+            if play == 'donor':
+                rows = torch.tensor(encode_instruments(donor_programs)[:C], dtype=torch.float).unsqueeze(0)
+            for at in range(0, len(starts), K):
+                part = starts[at:at + K]
+                live = len(part)
+                batch = WindowBatch(C, bars, T, U, [0] * K, part + [part[-1]] * (K - live))
+                res = model.transfer_styles(store, batch, bank, [entries] * K, instruments='pooled' if rows is None else rows, score=score,
+                                            live=live)
+                if rows is None:                                # the file's one decision: the later batches play the same
+                    rows, picked = res.instr_features[:1].clone(), res.decisions[0, :C].cpu().tolist()
+                    donor_programs = [_instrument_categories[i] for i in picked]
+                got.append((res, live))
+            scores[style_name] = _write_transfer(got, composition_info, song_info, donor_programs, C, R, U, bars, score,
+                                                 os.path.join(output_path, f'{composition_name} ({style_name} style).mid'))
+        jobs = jobs[:1]                                         # the reconstruction is transfer_windows', as ever
     for song, song_info, instruments, style_name in jobs:
         got = []
         for at in range(0, len(starts), K - 1):
@@ -120,6 +173,29 @@ def transfer_songs(model, composition_path, style_paths, output_path, bars=16, K
             scores[style_name] = dict(cosines=np.concatenate([style_cosines(res.style_sums)[:live] for res, live in got]).mean(0),
                                       pitched=NoteMetrics(retention[:, :-1]).sum(), unpitched=NoteMetrics(retention[:, -1]).sum())
     return scores if score else None
+
+
+def _write_transfer(got, composition_info, style_info, programs, C, R, U, bars, score, path):
+    """The file of one style from the batches' results [(TransferResult, live)], by transfer_songs' rules: the tempo of the mean
+    bpm_pred, the mode of the summed mode_pred, the records stitched and cut to R bars; returns the scores (None without)."""
+    from style.metrics import NoteMetrics, style_cosines
+    from style.sparse import crop_bars, stitch_records
+    each = lambda pick: [x for res, live in got for x in pick(res)[:live]]
+    bpm = np.asarray(each(lambda res: res.bpm_pred.cpu().tolist()), dtype=np.float64)
+    mode = np.asarray(each(lambda res: res.mode_pred.cpu().tolist()), dtype=np.float64).sum(0)
+    info = combine_info(style_info=style_info, melody_info=composition_info)
+    info['tempo'] = smf.bpm2tempo(round(float(bpm.mean())))
+    info['scale'] = dict(info['scale'], mode=major_mode if int(mode.argmax()) == 0 else minor_mode)
+    pitched = crop_bars(stitch_records(each(lambda res: res.pitched), bars), R)
+    unpitched = crop_bars(stitch_records(each(lambda res: res.unpitched), bars), R) if U else None
+    channels_info, unpitched_info = channel_slots(programs)
+    mid = decode_records(ChannelConverter(info), channels_info[:C], pitched, unpitched_info if U else None, unpitched)
+    mid.save(path)
+    if not score:
+        return None
+    retention = torch.cat([res.retention[:live] for res, live in got]).cpu()
+    return dict(cosines=np.concatenate([style_cosines(res.style_sums)[:live] for res, live in got]).mean(0),
+                pitched=NoteMetrics(retention[:, :-1]).sum(), unpitched=NoteMetrics(retention[:, -1]).sum())
 
 
 def get_model_input(path):

@@ -17,9 +17,14 @@ and their spread).
                Python surface doing the same work (extract_style, predict_song_info, apply_style, hard_output_sparse), and,
                under device events, the calls it adds at 64 clips: mst_clip_gather, mst_rolls_count, mst_rolls_compact and
                mst_style_sums.  The model's velocity biases are moved first so that 2 % of the cells are notes.
+  --styles     times the style bank instead of training: StyleTransferModel.encode_styles over the store (windows per second)
+               and transfer_styles — every clip a blend of two songs' means, instruments 'each' — for every K of --clips,
+               interleaved with transfer_windows at the same K on the same windows (the path without the bank: the three new
+               launches are the difference) and with the per-window Python surface with select_instruments on the host in the
+               loop; and, under device events, mst_style_put, mst_style_mix and mst_info_decide at 64 clips.
 One JSON line per measurement; --out writes them all to a file.
 Usage on the GPU box: python tools/window_rate.py [--songs 16] [--iters 150] [--runs 5] [--one-clip] [--kernels] [--eval
-                      [--eval-stride S]] [--transfer] [--out FILE]"""
+                      [--eval-stride S]] [--transfer] [--styles] [--out FILE]"""
 import argparse
 import json
 import os
@@ -346,6 +351,123 @@ def transfer_kernels(model, store, K, reps=50):
     return res
 
 
+def style_legs(model, store, songs, clips, iters, runs):
+    """Windows per second of encode_styles (a whole pass over the store per call), of transfer_styles (each clip a blend of two
+    songs' mean styles out of the bank, instruments decided per clip on the device) and of transfer_windows at the same K on the
+    same random windows, and of the per-window Python surface doing transfer_styles' work with the decision on the host:
+    extract_style, predict_song_info, select_instruments + encode_instruments (a download in the middle), apply_style,
+    hard_output_sparse x 2.  All legs are warmed up, then timed in turn `runs` times."""
+    from style.data import encode_instruments, prepare_input
+    from style.model import hard_output_sparse
+    from style.style_transfer import select_instruments
+    rng = np.random.default_rng(0)
+    windows = []
+    for name, (info, p, f, ins, u) in songs[:8]:
+        r0 = int(rng.integers(0, p.shape[1] - BARS + 1))
+        windows.append(prepare_input((name, (info, p[:, r0:r0 + BARS], f, ins, u[:, r0:r0 + BARS]))))
+    thin_predictions(model, windows)
+    dev = model._anchor().device
+    banks = {}
+
+    def encode(K):
+        def run(n):
+            for _ in range(n):
+                banks[K] = model.encode_styles(store, BARS, K)
+            return n * len(banks[K]), None
+        return run
+
+    def styles(K):
+        def run(n):
+            bank, ids = banks[K], sorted(banks[K].by_song)
+            for _ in range(n):
+                mix = [bank.blend([(ids[int(a)], .5), (ids[int(b)], .5)]) for a, b in rng.integers(0, len(ids), (K, 2))]
+                res = model.transfer_styles(store, store.sample(rng, K, BARS), bank, mix, instruments='each', capacity=TRANSFER_CAPACITY)
+            return K * n, res
+        return run
+
+    def plain(K):
+        def run(n):
+            for _ in range(n):
+                res = model.transfer_windows(store, store.sample(rng, K, BARS), rng.integers(0, K, K), capacity=TRANSFER_CAPACITY)
+            return K * n, res
+        return run
+    kept = []
+
+    def surface(n):
+        with torch.no_grad():
+            if not kept:
+                kept.extend(model.extract_style(*w)[0] for w in windows)
+            for i in range(n):
+                w, d = windows[i % len(windows)], (i * 5 + 3) % len(windows)
+                style = kept[d] * .5 + kept[(d + 1) % len(windows)] * .5
+                _, melody, rhythm = model.extract_style(*w)
+                ip, _, _ = model.predict_song_info(style, rhythm)
+                programs, _ = select_instruments(ip.cpu().numpy()[0], C + 1)
+                feats = torch.tensor(encode_instruments(programs[:C]), dtype=torch.float).to(dev).unsqueeze(0)
+                xp, xu = model.apply_style(style, melody, rhythm, feats, True)
+                res = hard_output_sparse(xp), hard_output_sparse(xu)
+        return n, res
+    legs = []
+    for K in clips:
+        legs += [(f'encode_styles, K = {K}', encode(K), 2), (f'transfer_styles, K = {K}', styles(K), max(iters // K, 4)),
+                 (f'transfer_windows, K = {K}', plain(K), max(iters // K, 4))]
+    legs.append(('extract_style / predict_song_info / select_instruments / apply_style / hard_output_sparse per window', surface, iters))
+    rates = {name: [] for name, _, _ in legs}
+    for name, run, n in legs:                              # eager, capture + replay, replays; the plans of every shape
+        run(3)
+        torch.cuda.synchronize()
+    for _ in range(runs):
+        for name, run, n in legs:                          # interleaved
+            t0 = time.perf_counter()
+            done, _ = run(n)
+            torch.cuda.synchronize()
+            rates[name].append(done / (time.perf_counter() - t0))
+    model.check_device_status()
+    return [dict(what=name, bars=BARS, C=C, T=T, unit='windows/s', **spread(rates[name])) for name, _, _ in legs]
+
+
+def style_kernels(model, store, K, entries=8, reps=50):
+    """Microseconds, under device events, of the three launches the style bank adds, at K clips: mst_style_put of the K style
+    slots into a bank, mst_style_mix of `entries` rows per clip back into them, and mst_info_decide on the K predictions."""
+    from style import _native
+    from style.data import group_of_instrument
+    native, dev = _native.get(), model._anchor().device
+    plan = model._plan(C, BARS, T, True, dev, clips=K)
+    ws = plan.new_ws()
+    ws[:K * plan.clip_stride].uniform_(-1, 1)
+    slot = lambda name: ws.data_ptr() + 4 * plan.slot(name)[0]
+    size = plan.slot('style')[2]
+    bank = torch.zeros(4 * K, size, device=dev)
+    rows = torch.arange(K, dtype=torch.int32, device=dev)
+    offsets = torch.arange(0, (K + 1) * entries, entries, dtype=torch.int32, device=dev)
+    idx = torch.randint(0, K, (K * entries,), dtype=torch.int32, device=dev)
+    w = torch.full((K * entries,), 1. / entries, device=dev)
+    rec = torch.zeros(K, C + 2, dtype=torch.int32, device=dev)
+    stream = _native.current_stream(dev)
+    n_logits = plan.slot('instruments_pred')[2]
+    calls = (('mst_style_put', lambda: native.style_put(slot('style'), plan.clip_stride, bank, 4 * K, size, rows, K, size, stream)),
+             (f'mst_style_mix, {entries} entries per clip', lambda: native.style_mix(bank, 4 * K, size, offsets, idx, w, K * entries, slot('style'),
+                                                                                     plan.clip_stride, K, size, stream)),
+             ('mst_info_decide', lambda: native.info_decide(slot('instruments_pred'), slot('mode_pred'), slot('bpm_pred'), plan.clip_stride,
+                                                            n_logits, group_of_instrument, plan.slot('instr')[2] // C - (n_logits - 1), C, K,
+                                                            False, None, slot('instr'), slot('mode'), slot('bpm'), plan.clip_stride, rec,
+                                                            stream)))
+    res = []
+    for name, fn in calls + calls:                         # alternated
+        fn()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            times.append(a.elapsed_time(b) * 1e3)
+        res.append(dict(what=name, K=K, C=C, style_size=size, unit='us', **spread(times)))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--songs', type=int, default=16)
@@ -357,6 +479,7 @@ def main():
     ap.add_argument('--eval', action='store_true')
     ap.add_argument('--eval-stride', type=int, default=None)
     ap.add_argument('--transfer', action='store_true')
+    ap.add_argument('--styles', action='store_true')
     ap.add_argument('--out')
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -377,9 +500,12 @@ def main():
     if args.transfer:
         results += transfer_legs(model, store, songs, args.clips, args.iters, args.runs)
         results += transfer_kernels(model, store, 64)
+    if args.styles:
+        results += style_legs(model, store, songs, args.clips, args.iters, args.runs)
+        results += style_kernels(model, store, 64)
     opt = FusedAdam(model)
     opt.zero_grad()
-    for K in [] if args.eval or args.transfer else args.clips:
+    for K in [] if args.eval or args.transfer or args.styles else args.clips:
         results.append(windowed(model, opt, store, K, args.iters, args.runs))
     if args.one_clip:
         results.append(one_clip(build_model(seed=108), songs, args.iters * 16, args.runs))
