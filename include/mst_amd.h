@@ -281,6 +281,28 @@ typedef struct { int32_t first, count, src_bars, r0; } mst_window;   /* 16 bytes
 int32_t mst_clip_window(const int32_t* cells, const float* feats, const mst_window* win, int32_t n_clips, int32_t channels,
                         int32_t bars, int64_t bar_cells, int32_t nfeat, float* out, mst_stream stream);
 
+/* ---- rotating song store: one refresh of the pools and tables that mst_clip_window / mst_window_inputs read, as ONE batched,
+ * segmented, bit-exact copy.  Everything that varies is read ON THE DEVICE, so the launch arguments are the same for every
+ * refresh.  blob (a DEVICE staging buffer of blob_words 32-bit words) holds one refresh:
+ *   blob[0]              the segment count n, clamped to [0, max_segments]; blob[1..3] are not read
+ *   blob[4 + 4 i ..]     segment i (mst_segment; every field counts 32-bit words)
+ *   the payload          behind the header of max_segments segments; src_off counts from the start of the blob
+ * Segment i copies `words` words from blob + src_off to (int32_t*)dst[dst] + dst_off, bit for bit (the words travel as integers:
+ * NaN payloads and -0.0 survive) — if 0 <= dst < MST_ADMIT_DSTS, dst[dst] != NULL, words >= 0, the source range lies inside
+ * [4 + 4 max_segments, blob_words) and the destination range inside [0, dst_words[dst]); otherwise NOTHING of that segment is
+ * written.  status[i], for EVERY i < max_segments on EVERY launch: 0 = copied or unused (i >= n), 1 = refused; written with
+ * plain stores, never cleared by the caller.  Where source and destination address agree modulo 16 the copy moves 16 bytes at
+ * a time between a word-wise head and tail; where they do not it moves words.  Every pointer needs 4-byte alignment only.
+ * mst_clip_scatter's promises hold: nothing outside the named destination ranges is written, one launch on a grid sized from
+ * the device's compute units, enqueue-only on `stream` (no allocation, no host synchronisation, capturable), no atomics,
+ * bit-reproducible.  Destination ranges that overlap within one call are the caller's business.  MST_ERR_ARG, and nothing is
+ * launched: a null blob / dst / dst_words / status, max_segments < 1, blob_words < 4 + 4 max_segments, a pointer that is not
+ * 4-byte aligned. */
+enum { MST_ADMIT_DSTS = 16 };
+typedef struct { int32_t dst, dst_off, src_off, words; } mst_segment;   /* 16 bytes, all in 32-bit words */
+int32_t mst_store_admit(const int32_t* blob, int64_t blob_words, int32_t max_segments, void* const dst[MST_ADMIT_DSTS],
+                        const int64_t dst_words[MST_ADMIT_DSTS], int32_t* status /* max_segments int32 */, mst_stream stream);
+
 /* ---- sparse clip output: the sorted note records of a dense roll, built on the device — the inverse of mst_clip_scatter, so
  * that inference downloads the notes (24 bytes per pitched record) instead of the whole roll.  x: n_cells x nfeat floats.
  *   MST_ROLL_NONZERO  a cell is a record when the float32 BIT PATTERN of any of its features is non-zero (-0.0 and NaN are

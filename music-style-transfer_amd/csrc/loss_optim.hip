@@ -959,6 +959,131 @@ extern "C" int32_t mst_clip_window(const int32_t* cells, const float* feats, con
     return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
 }
 
+// ------------------------------------------------------------------ rotating song store (mst_store_admit)
+// One refresh of a SongStore ring: a staged blob — a header of segments, then their payload — is copied into the store's pools
+// and tables, bit for bit, in ONE launch whose arguments never change.  The header is read here, on the device, ADMIT_BATCH
+// segments at a time: every lane checks one segment and counts its chunks of ADMIT_CHUNK words, the workgroup scans the counts
+// in LDS, and the fixed grid strides over the batch's chunks (a table row is one chunk, a feats array a hundred).  A chunk is cut
+// on the DESTINATION's 16-byte grid (`shift`, as the scatter cuts its slices): where source and destination are 16 bytes apart
+// modulo 16 a lane moves four words with one 16-byte load and store, the ragged head and tail word by word; where they are not,
+// the chunk goes word by word, a wave reading and writing consecutive words.  Words travel as integers: NaN payloads and -0.0
+// arrive as they left.  Workgroup 0 writes the status words, every one of them on every launch.
+#define ADMIT_THREADS 256
+#define ADMIT_BATCH 256          // segments checked per round: one per lane
+#define ADMIT_CHUNK 1024         // words per chunk: one 16-byte move per lane
+
+struct alignas(16) admit_word4 { int32_t x, y, z, w; };
+struct admit_dsts { int32_t* ptr[MST_ADMIT_DSTS]; int64_t words[MST_ADMIT_DSTS]; };
+
+__global__ __launch_bounds__(ADMIT_THREADS) void store_admit_kernel(const int32_t* blob, int64_t blob_words, int max_segments,
+                                                                    admit_dsts dsts, int32_t* status) {
+    __shared__ int s_scan[2][ADMIT_BATCH];                 // inclusive prefix of the batch's chunk counts (double-buffered scan)
+    __shared__ int s_dst[ADMIT_BATCH], s_dst_off[ADMIT_BATCH], s_src_off[ADMIT_BATCH], s_words[ADMIT_BATCH];
+    const int tid = threadIdx.x;
+    int n = blob[0];
+    n = n < 0 ? 0 : (n > max_segments ? max_segments : n);
+    const int64_t payload = 4 + 4 * (int64_t)max_segments;
+    for (int base = 0; base < max_segments; base += ADMIT_BATCH) {      // workgroup-uniform
+        const int i = base + tid;
+        int chunks = 0;
+        mst_segment sg = {0, 0, 0, 0};
+        if (i < max_segments) {
+            int refused = 0;
+            if (i < n) {
+                sg = *reinterpret_cast<const mst_segment*>(blob + 4 + 4 * (int64_t)i);
+                const int64_t w = sg.words;
+                bool ok = sg.dst >= 0 && sg.dst < MST_ADMIT_DSTS && w >= 0 && sg.src_off >= payload && sg.src_off + w <= blob_words &&
+                          sg.dst_off >= 0;
+                if (ok) ok = dsts.ptr[sg.dst] != nullptr && sg.dst_off + w <= dsts.words[sg.dst];
+                refused = ok ? 0 : 1;
+                if (ok && w > 0) {
+                    const int shift = (int)(((uintptr_t)(dsts.ptr[sg.dst] + sg.dst_off) & 15) / 4);
+                    chunks = (int)((shift + w + ADMIT_CHUNK - 1) / ADMIT_CHUNK);
+                }
+            }
+            if (blockIdx.x == 0) status[i] = refused;
+        }
+        s_dst[tid] = sg.dst;
+        s_dst_off[tid] = sg.dst_off;
+        s_src_off[tid] = sg.src_off;
+        s_words[tid] = sg.words;                           // read only where the segment has chunks, i.e. was accepted
+        s_scan[0][tid] = chunks;
+        __syncthreads();
+        int cur = 0;
+        for (int d = 1; d < ADMIT_BATCH; d <<= 1) {        // Hillis-Steele: a batch of 256 chunk counts sums below 2^31
+            s_scan[cur ^ 1][tid] = s_scan[cur][tid] + (tid >= d ? s_scan[cur][tid - d] : 0);
+            cur ^= 1;
+            __syncthreads();
+        }
+        const int* pre = s_scan[cur];
+        const int total = pre[ADMIT_BATCH - 1];
+        for (int g = blockIdx.x; g < total; g += gridDim.x) {           // workgroup-uniform
+            int lo = 0, hi = ADMIT_BATCH - 1;              // the first segment whose inclusive prefix exceeds g
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (pre[mid] > g) hi = mid; else lo = mid + 1;
+            }
+            const int c = g - (lo ? pre[lo - 1] : 0);
+            const int32_t* src = blob + s_src_off[lo];
+            int32_t* dst = dsts.ptr[s_dst[lo]] + s_dst_off[lo];
+            const int64_t words = s_words[lo];
+            const int shift = (int)(((uintptr_t)dst & 15) / 4);
+            // v = word index + shift: v = 0 (mod 4) is a 16-byte boundary of the destination
+            const int64_t v0 = (int64_t)c * ADMIT_CHUNK, vend = shift + words;
+            if ((((uintptr_t)src ^ (uintptr_t)dst) & 15) == 0) {
+                const int64_t v = v0 + 4 * tid;
+                if (v >= shift && v + 4 <= vend) {
+                    *reinterpret_cast<admit_word4*>(dst + (v - shift)) = *reinterpret_cast<const admit_word4*>(src + (v - shift));
+                } else {                                                // the ragged head and tail of the segment
+                    for (int j = 0; j < 4; ++j)
+                        if (v + j >= shift && v + j < vend) dst[v + j - shift] = src[v + j - shift];
+                }
+            } else {
+                for (int j = 0; j < ADMIT_CHUNK / ADMIT_THREADS; ++j) {
+                    const int64_t v = v0 + j * ADMIT_THREADS + tid;
+                    if (v >= shift && v < vend) dst[v - shift] = src[v - shift];
+                }
+            }
+        }
+        __syncthreads();                                   // the LDS tables are rewritten by the next batch
+    }
+}
+
+// compute units of the current device, asked once per device (the grid of mst_store_admit is sized from it)
+static int admit_cus() {
+#ifdef HIPSIM
+    return 4;
+#else
+    static int cached[64] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0) return 0;
+    if (dev < 64 && cached[dev] > 0) return cached[dev];
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    if (dev < 64) cached[dev] = cus;
+    return cus;
+#endif
+}
+
+extern "C" int32_t mst_store_admit(const int32_t* blob, int64_t blob_words, int32_t max_segments, void* const dst[MST_ADMIT_DSTS],
+                                   const int64_t dst_words[MST_ADMIT_DSTS], int32_t* status, mst_stream stream) {
+    if (!blob || !dst || !dst_words || !status || max_segments < 1 || blob_words < 4 + 4 * (int64_t)max_segments ||
+        ((uintptr_t)blob & 3) || ((uintptr_t)status & 3))
+        return MST_ERR_ARG;
+    admit_dsts d;
+    for (int k = 0; k < MST_ADMIT_DSTS; ++k) {
+        if ((uintptr_t)dst[k] & 3) return MST_ERR_ARG;
+        d.ptr[k] = static_cast<int32_t*>(dst[k]);
+        d.words[k] = dst_words[k];
+    }
+    const int cus = admit_cus();
+    if (cus < 1) return MST_ERR_LAUNCH;
+    // two workgroups per compute unit: a refresh of a few songs is some hundred chunks, and 512 lanes keep a CU's loads in flight
+    hipLaunchKernelGGL(store_admit_kernel, dim3((unsigned)(2 * cus)), dim3(ADMIT_THREADS), 0, (hipStream_t)stream, blob, blob_words,
+                       (int)max_segments, d, status);
+    return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
+}
+
 // ------------------------------------------------------------------ sparse clip output (mst_roll_count, mst_roll_compact)
 // The inverse of the scatter: the sorted (cell, features) records of a dense roll, so that only the notes go back to the host.
 // An ordered stream compaction in the usual three steps — per-slice counts, an exclusive scan of the counts, emit — with no atomics

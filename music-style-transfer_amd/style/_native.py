@@ -50,6 +50,32 @@ METRIC_WORDS = 8                    # mst_amd.h MST_METRIC_WORDS: doubles per re
 ROW_FIELDS = 8                      # mst_amd.h MST_ROW_FIELDS: pieces of a table row one mst_window_inputs call places
 STYLE_SUM_WORDS = 8                 # mst_amd.h MST_STYLE_SUM_WORDS: doubles per clip of mst_style_sums
 EVAL_ACC_WORDS = 41                 # mst_amd.h MST_EVAL_ACC_WORDS: doubles of a round's running sum (mst_eval_accumulate)
+ADMIT_DSTS = 16                     # mst_amd.h MST_ADMIT_DSTS: destinations one mst_store_admit call names
+SEGMENT_WORDS = 4                   # mst_amd.h mst_segment: int32 words per segment of mst_store_admit (dst, dst_off, src_off, words)
+
+
+class AdmitDsts:
+    """The two destination arrays of mst_store_admit — `ptr[k]` an address (0 = NULL) and `words[k]` its length in 32-bit words —
+    made once and passed again with every refresh."""
+
+    def __init__(self, dsts=()):
+        self.ptr, self.words = (C.c_void_p * ADMIT_DSTS)(), (C.c_int64 * ADMIT_DSTS)()
+        dsts = list(dsts)
+        if len(dsts) > ADMIT_DSTS:
+            raise MstError(f'mst_store_admit names {ADMIT_DSTS} destinations at most, not {len(dsts)}')
+        for k, d in enumerate(dsts):
+            self.set(k, *d) if isinstance(d, tuple) else self.set(k, d)
+
+    def set(self, k, t, words=None):
+        """Destination k: a 4-byte-element tensor (all of it), or an address and a number of words; None = NULL."""
+        if t is None:
+            self.ptr[k], self.words[k] = None, 0
+        elif isinstance(t, int):
+            self.ptr[k], self.words[k] = t or None, int(words)
+        else:
+            if t.element_size() != 4 or not t.is_contiguous():
+                raise MstError('mst_store_admit copies into contiguous tensors of 4-byte elements')
+            self.ptr[k], self.words[k] = t.data_ptr(), t.numel() if words is None else int(words)
 
 
 class RowFields(C.Structure):
@@ -134,6 +160,7 @@ _SIGS = {
     'mst_hard_output': (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P]),
     'mst_clip_scatter': (C.c_int32, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _P, _P]),
     'mst_clip_window': (C.c_int32, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _P, _P]),
+    'mst_store_admit': (C.c_int32, [_P, C.c_int64, C.c_int32, C.POINTER(C.c_void_p * 16), C.POINTER(C.c_int64 * 16), _P, _P]),
     'mst_roll_slices': (C.c_int64, [C.c_int64]),
     'mst_roll_count': (C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
     'mst_roll_compact': (C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P]),
@@ -237,6 +264,14 @@ class Native:
         addr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()
         check(self.lib.mst_clip_window(addr(cells), addr(feats), addr(win), int(n_clips), int(channels), int(bars), int(bar_cells),
                                        int(nfeat), addr(out), stream), 'mst_clip_window')
+
+    def store_admit(self, blob, blob_words, max_segments, dsts, status, stream=None):
+        """mst_store_admit: copy the segments a staged `blob` (int32, on the device) lists into the destinations of `dsts` (an
+        AdmitDsts), bit for bit; the segment count and the segments are read on the device, `status` (int32, max_segments) says
+        per segment 0 = copied or unused, 1 = refused.  Tensors on one device or raw addresses.  Enqueue-only."""
+        addr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()
+        check(self.lib.mst_store_admit(addr(blob), int(blob_words), int(max_segments), C.byref(dsts.ptr), C.byref(dsts.words),
+                                       addr(status), stream), 'mst_store_admit')
 
     def roll_slices(self, n_cells):
         """mst_roll_slices: slices the compaction kernels cut `n_cells` into; the workspace of roll_count holds one int32 more."""

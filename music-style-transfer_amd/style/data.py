@@ -4,7 +4,8 @@ one-hot encoding, MIDI file -> model input (`iter_inputs`, `get_input`), `prepar
 device (one H2D copy per tensor).  `prepare_input_sparse` is its counterpart for real songs: the note
 tensors stay on the host as sorted note records (`SparseRoll`, `SparseClip`) and are expanded on the
 device by mst_clip_scatter.  `SongStore` keeps the records of many songs on the device and `WindowBatch` names K equally
-shaped windows of them (mst_clip_window crops them there); `StyleBank` keeps style vectors there.  sklearn's OneHotEncoder and pandas are not used: categories are the
+shaped windows of them (mst_clip_window crops them there) — append-only, or with `resident=N` a fixed ring that `admit` rotates
+songs through (mst_store_admit); `StyleBank` keeps style vectors there.  sklearn's OneHotEncoder and pandas are not used: categories are the
 sorted distinct values, which is what `categories='auto'` produces (style/data.py:23-27).
 """
 import numpy as np
@@ -260,28 +261,299 @@ def _not_while_capturing(dev):
         raise RuntimeError('SongStore: a device pool or table would have to grow while a stream is capturing; add the songs first')
 
 
+class SongEvicted(LookupError):
+    """A song id of a ring SongStore whose song has left the device."""
+
+
+RING_ALIGN = 4            # records: a song's first record is a multiple of it, so cells (x 1) and feats (x 5, x 2) start on 16 bytes
+
+
+def ring_place(head, count, capacity):
+    """Where the next song of `count` records goes in a ring pool of `capacity` records whose head (the record behind the last
+    placed song) is `head`: -> (first, new head).  `first` is `head` rounded up to a multiple of RING_ALIGN records, or 0 when
+    the song would reach past the end from there.  Pure: says nothing about what lives at that place."""
+    first = -(-int(head) // RING_ALIGN) * RING_ALIGN
+    if first + count > capacity:
+        first = 0
+    return first, first + int(count)
+
+
+def _up4(n):
+    return -(-int(n) // 4) * 4
+
+
 class SongStore:
     """Songs resident on the device, for training on windows of them (StyleTransferModel.train_windows).  `add` appends a
     song's pitched and unpitched note records to two device pools (grown by doubling, never during a capture) and its small
     inputs — mode, bpm, instrument features, used instruments, bpm target — as a row of a device table; the host keeps the
     cells, `(C, R, T)` and the percussion flag.  Songs are bucketed by `(C, T, has percussion)`: the windows of one bucket have
     one shape once their number of bars is chosen, which is what a batched plan needs.  `sample` draws K windows of a bucket;
-    mst_clip_window crops them on the device, so no note data crosses the bus inside the training loop."""
-    TRIES = 8             # windows tried per drawn song before another song is drawn
+    mst_clip_window crops them on the device, so no note data crosses the bus inside the training loop.
 
-    def __init__(self, device=device, capacity=1 << 14):
+    `resident=N` makes the store a RING for training on more songs than fit: both pools hold exactly `capacity` records at
+    addresses that never change, songs come in by `admit` — a group with one upload and one mst_store_admit launch — and the
+    oldest leave to make room, so that at most N are resident.  Ids keep counting; `songs[id]` of an evicted song is None, and
+    naming one raises SongEvicted.  Nothing a captured graph has baked in moves, so train_windows, eval_windows and transfer_*
+    keep replaying across refreshes.  `resident=None` is the append-only store."""
+    TRIES = 8             # windows tried per drawn song before another song is drawn
+    STAGE_SLOTS = 4       # pinned blobs of `admit`, each reused only after the copy that last read it
+
+    def __init__(self, device=device, capacity=1 << 14, resident=None):
         self.device = torch.device(device)
         self.songs = []                                   # per song id: dict of host-side facts
         self.pools = {n_feat: _RecordPool(n_feat, self.device, capacity) for n_feat in (5, 2)}
         self.buckets = {}                                 # (C, T, percussion) -> dict(songs, table, fields)
         self._silent = set()                              # (song, bars): no window of that many bars passes the silence rule
+        self.resident_limit = None if resident is None else int(resident)
+        if self.resident_limit is not None:
+            if self.resident_limit < 1 or int(capacity) < 1:
+                raise ValueError('SongStore: resident and capacity must be at least 1')
+            self.capacity = int(capacity)
+            self._live = []                               # resident ids, oldest first
+            self._heads = {5: 0, 2: 0}
+            self._stage = [dict(buf=None, done=None) for _ in range(self.STAGE_SLOTS)]
+            self._stage_at = 0
+            self._blob = self._status = None              # device staging buffer, status words (one row per launch)
+            self._max_segments, self._launched = 64, []   # segments per launch of the last admit
+            self.admit_native = None                      # a store on 'cpu' copies with torch unless given a style._native.Native
 
     def __len__(self):
         return len(self.songs)
 
+    # ---- the ring
+    def resident(self):
+        """The ids of the songs on the device, oldest first."""
+        if self.resident_limit is None:
+            return list(range(len(self.songs)))
+        return list(self._live)
+
+    def evicted(self, song):
+        return self.songs[song] is None
+
+    def _song(self, song):
+        s = self.songs[song]
+        if s is None:
+            raise SongEvicted(f'song {song} has left the store (SongStore.admit evicted it); draw the batch after the refresh')
+        return s
+
+    def _evict_oldest(self):
+        song = self._live.pop(0)
+        s, self.songs[song] = self.songs[song], None
+        bucket = self.buckets[s['key']]
+        bucket['songs'].remove(song)
+        bucket['free'].append(s['row'])
+        bucket['views'].pop(song, None)
+        self._silent = {(i, bars) for i, bars in self._silent if i != song}
+
+    def _overlaps(self, nfeat, first, count):
+        name = 'pitched' if nfeat == 5 else 'unpitched'
+        for song in self._live:
+            at = self.songs[song][name]
+            if at is not None and at[0] < first + count and first < at[0] + at[1]:
+                return True
+        return False
+
+    def _bookkeeping(self):
+        return dict(n=len(self.songs), songs={i: self.songs[i] for i in self._live}, live=list(self._live), heads=dict(self._heads),
+                    silent=set(self._silent), keys=set(self.buckets),
+                    buckets={key: (list(b['songs']), list(b['free']), dict(b['views']), b['table'], b['rows']) for key, b in self.buckets.items()})
+
+    def _restore(self, was):
+        del self.songs[was['n']:]
+        for i, s in was['songs'].items():
+            self.songs[i] = s
+        self._live, self._heads, self._silent = was['live'], was['heads'], was['silent']
+        for key in set(self.buckets) - was['keys']:
+            del self.buckets[key]
+        for key, (songs, free, views, table, rows) in was['buckets'].items():
+            self.buckets[key].update(songs=songs, free=free, views=views, table=table, rows=rows)
+        for nfeat, head in self._heads.items():
+            self.pools[nfeat].used = head
+
+    def admit(self, clips):
+        """Take a group of SparseClips into a ring store (`resident=N`); returns their ids.  Silence is treated as in `add`, and a
+        song whose pitched or unpitched records exceed `capacity` is refused (ValueError) — either before anything changes.  For
+        each clip in turn the oldest resident songs are evicted until at most N are resident, the new one counted, and neither
+        pool's place for it (`ring_place`) overlaps a live song.  The whole group then travels as ONE pinned blob — a header of
+        segments, then per song its pitched cells and feats, unpitched cells and feats and its table row, every offset a
+        multiple of 4 words — with one non-blocking copy into a device staging buffer and one mst_store_admit launch (more than
+        one only when the group touches more than 12 buckets).
+
+        Everything is enqueued on the CURRENT stream, which must be the stream the store's consumers (train_windows,
+        eval_windows, transfer_*) run on: stream order is what keeps a crop that is still in flight from reading records this
+        call overwrites.  After the launch nothing else is enqueued and nothing is waited for; `check` reads the status words
+        where the caller synchronises anyway.  A WindowBatch drawn before this call may name evicted songs: it raises
+        SongEvicted when used."""
+        if self.resident_limit is None:
+            raise ValueError('SongStore.admit: the store was made without resident=N; use add')
+        from style import _native
+        new = []
+        for clip in clips:                                # refusals first: nothing has changed yet
+            clip = clip.drop_silent()
+            if clip is None:
+                raise ValueError('SongStore.admit: a clip has no pitched notes (SparseClip.drop_silent() is None)')
+            pitched, unpitched = clip.pitched_channels, clip.unpitched_channels
+            _, C, R, T = pitched.shape[:4]
+            if unpitched is not None and tuple(unpitched.shape[:4]) != (1, 1, R, T):
+                raise ValueError(f'unpitched roll {unpitched.shape} does not match the pitched roll {pitched.shape}')
+            if max(pitched.count, 0 if unpitched is None else unpitched.count) > self.capacity:
+                raise ValueError(f'SongStore.admit: a song of {pitched.count} pitched and {0 if unpitched is None else unpitched.count} '
+                                 f'unpitched records, the ring holds {self.capacity}')
+            key = (C, T, unpitched is not None)
+            used = get_used_instruments(clip.instruments_features, unpitched)
+            parts = (clip.mode, clip.bpm, clip.instruments_features, used, torch.tensor([float(clip.bpm_target)]))
+            row = torch.cat([t.reshape(-1).float() for t in parts])
+            ends = np.cumsum([t.numel() for t in parts]).tolist()
+            known = self.buckets.get(key)
+            if known is not None and known['fields'][-1][1] != ends[-1]:
+                raise ValueError(f'small inputs of {ends[-1]} floats, the bucket {key} holds rows of {known["fields"][-1][1]}')
+            new.append((clip, key, row, ends))
+        if not new:
+            return []
+        was = self._bookkeeping()
+        try:
+            ids = self._admit(new, _native)
+        except BaseException:
+            self._restore(was)
+            raise
+        return ids
+
+    def _admit(self, new, _native):
+        sounding = lambda roll: roll.cells.numpy()[np.any(roll.feats.numpy() != 0, axis=1)].astype(np.int64)
+        ids, grown = [], set()
+        for clip, key, row, ends in new:
+            pitched, unpitched = clip.pitched_channels, clip.unpitched_channels
+            rolls = [(5, pitched)] + ([(2, unpitched)] if unpitched is not None else [])
+            while True:
+                place = {nfeat: ring_place(self._heads[nfeat], roll.count, self.capacity) for nfeat, roll in rolls}
+                if len(self._live) < self.resident_limit and not any(self._overlaps(nfeat, place[nfeat][0], roll.count)
+                                                                      for nfeat, roll in rolls):
+                    break
+                self._evict_oldest()
+            bucket = self.buckets.get(key)
+            if bucket is None:
+                # rows padded to 16 bytes: a row's copy is as aligned as the records'
+                bucket = self.buckets[key] = dict(songs=[], fields=list(zip([0] + ends[:-1], ends)), views={}, free=[], rows=0,
+                                                  table=torch.zeros(16, _up4(ends[-1]), dtype=torch.float32, device=self.device))
+            if bucket['free']:
+                at = bucket['free'].pop(0)
+            else:
+                at, bucket['rows'] = bucket['rows'], bucket['rows'] + 1
+                if at == bucket['table'].shape[0]:
+                    _not_while_capturing(self.device)
+                    table = bucket['table'].new_zeros(2 * at, bucket['table'].shape[1])
+                    table[:at].copy_(bucket['table'])
+                    bucket['table'], bucket['views'] = table, {}
+                    grown.add(key)
+            C, R, T = key[0], pitched.shape[2], key[1]
+            song = dict(C=C, R=R, T=T, percussion=unpitched is not None, key=key, row=at, pitched=(place[5][0], pitched.count),
+                        pitched_cells=sounding(pitched), unpitched=None)
+            if unpitched is not None:
+                song.update(unpitched=(place[2][0], unpitched.count), unpitched_cells=sounding(unpitched))
+            for nfeat, _ in rolls:
+                self._heads[nfeat] = self.pools[nfeat].used = place[nfeat][1]
+            self.songs.append(song)
+            self._live.append(len(self.songs) - 1)
+            bucket['songs'].append(len(self.songs) - 1)
+            ids.append(len(self.songs) - 1)
+        # the copies: of the group's songs that are still resident (a later member may have evicted an earlier one), so that
+        # no two segments of a launch name the same words
+        fixed = [self.pools[5].cells, self.pools[5].feats, self.pools[2].cells, self.pools[2].feats]
+        todo = [(i, clip, row) for i, (clip, _, row, _) in zip(ids, new) if self.songs[i] is not None]
+        launches, at = [], 0
+        while at < len(todo):                             # groups of at most ADMIT_DSTS - 4 buckets
+            keys, end = [], at
+            while end < len(todo):
+                key = self.songs[todo[end][0]]['key']
+                if key not in keys:
+                    if len(keys) == _native.ADMIT_DSTS - len(fixed):
+                        break
+                    keys.append(key)
+                end += 1
+            launches.append((keys, todo[at:end]))
+            at = end
+        packed = []
+        for keys, part in launches:
+            segments = []                                 # (dst, dst_off, the int32 words)
+            for i, clip, row in part:
+                s = self.songs[i]
+                for slot, (name, roll) in enumerate((('pitched', clip.pitched_channels), ('unpitched', clip.unpitched_channels))):
+                    if roll is None:
+                        continue
+                    first, nfeat = s[name][0], (5, 2)[slot]
+                    segments.append((2 * slot, first, roll.cells.numpy().reshape(-1)))
+                    segments.append((2 * slot + 1, first * nfeat, roll.feats.numpy().reshape(-1).view(np.int32)))
+                table = self.buckets[s['key']]['table']
+                segments.append((len(fixed) + keys.index(s['key']), s['row'] * table.shape[1], row.numpy().view(np.int32)))
+            packed.append((fixed + [self.buckets[key]['table'] for key in keys], segments))
+        self._reserve(max(len(segments) for _, segments in packed), max(sum(_up4(len(w)) for _, _, w in segments) for _, segments in packed),
+                      len(packed))
+        self._launched = []
+        for n, (dsts, segments) in enumerate(packed):
+            self._launch(n, dsts, segments, _native)
+        return ids
+
+    def _reserve(self, n_segments, payload_words, n_launches):
+        """Room in the device staging buffer and the status words for launches of that size; they grow outside a capture only."""
+        max_segments = self._max_segments
+        while max_segments < n_segments:
+            max_segments *= 2
+        need = 4 + 4 * max_segments + payload_words
+        if self._blob is None or max_segments > self._max_segments or need > self._blob.numel() or n_launches > self._status.shape[0]:
+            _not_while_capturing(self.device)
+            size = 1 << 12 if self._blob is None else self._blob.numel()
+            while size < need:
+                size *= 2
+            self._max_segments = max_segments
+            self._blob = torch.zeros(size, dtype=torch.int32, device=self.device)
+            self._status = torch.zeros(n_launches, max_segments, dtype=torch.int32, device=self.device)
+
+    def _launch(self, n, dsts, segments, _native):
+        """One blob: packed into a pinned slot, uploaded, copied out on the device."""
+        cuda = self.device.type == 'cuda'
+        slot = self._stage[self._stage_at % len(self._stage)]
+        self._stage_at += 1
+        if slot['done'] is not None and not slot['done'].query():
+            slot['done'].synchronize()
+        if slot['buf'] is None or slot['buf'].numel() < self._blob.numel():
+            _not_while_capturing(self.device)
+            slot['buf'] = torch.zeros(self._blob.numel(), dtype=torch.int32, pin_memory=cuda)
+        host = slot['buf'].numpy()
+        host[:4] = (len(segments), 0, 0, 0)
+        at = 4 + 4 * self._max_segments
+        for k, (dst, dst_off, words) in enumerate(segments):
+            host[4 + 4 * k:8 + 4 * k] = (dst, dst_off, at, len(words))
+            host[at:at + len(words)] = words
+            at += _up4(len(words))
+        native = _native.get() if cuda else self.admit_native
+        if native is None:                                # a store on the host: the same segments as torch copies
+            for dst, dst_off, src_off, words in host[4:4 + 4 * len(segments)].reshape(-1, 4).tolist():
+                dsts[dst].view(-1).view(torch.int32)[dst_off:dst_off + words].copy_(slot['buf'][src_off:src_off + words])
+            self._status[n].zero_()
+        else:
+            self._blob[:at].copy_(slot['buf'][:at], non_blocking=True)
+            if cuda:
+                slot['done'] = slot['done'] or torch.cuda.Event()
+                slot['done'].record()
+            native.store_admit(self._blob, self._blob.numel(), self._max_segments, _native.AdmitDsts(dsts), self._status[n],
+                               _native.current_stream(self.device))
+        self._launched.append(len(segments))
+
+    def check(self):
+        """Download the status words of the last `admit` and raise if mst_store_admit refused a segment (it never does unless
+        the bookkeeping here is wrong).  Synchronises: call it where the loop synchronises anyway."""
+        if self.resident_limit is None or not self._launched:
+            return
+        status = self._status[:len(self._launched)].cpu()
+        bad = [(n, k) for n, count in enumerate(self._launched) for k in np.flatnonzero(status[n].numpy()).tolist()]
+        if bad:
+            raise RuntimeError(f'SongStore.admit: mst_store_admit refused (launch, segment) {bad[:8]} of {self._launched} segments')
+
     def add(self, clip):
         """Take a SparseClip in; returns the song's id.  A clip whose percussion is silent is stored without it, as
-        `SparseClip.drop_silent` would; one without pitched notes is refused (ValueError)."""
+        `SparseClip.drop_silent` would; one without pitched notes is refused (ValueError).  On a ring store: `admit([clip])[0]`."""
+        if self.resident_limit is not None:
+            return self.admit([clip])[0]
         clip = clip.drop_silent()
         if clip is None:
             raise ValueError('SongStore.add: the clip has no pitched notes (SparseClip.drop_silent() is None)')
@@ -318,13 +590,13 @@ class SongStore:
         return len(self.songs) - 1
 
     def bucket_of(self, song):
-        return self.songs[song]['key']
+        return self._song(song)['key']
 
     # ---- windows
     def window_sounds(self, song, r0, bars):
         """train-model.py:105-109 applied to a window: it holds a sounding pitched note and, for a song with percussion, a
         sounding unpitched one (a silent roll makes the loss's masked means 0 / 0).  Decided on the host cells."""
-        s = self.songs[song]
+        s = self._song(song)
         per_bar = s['T'] * 10 * 56
         bounds = [(c * s['R'] + r0 + b) * per_bar for c in range(s['C']) for b in (0, bars)]
         at = np.searchsorted(s['pitched_cells'], bounds).reshape(-1, 2)
@@ -415,9 +687,10 @@ class SongStore:
     def describe(self, batch, out):
         """Fill `out` (a host int32 array (2, K, 4)) with the mst_window descriptors of the batch: row 0 for the pitched
         rolls, row 1 for the unpitched ones (zeros without percussion)."""
+        rows = [(self._song(song), r0) for song, r0 in zip(batch.songs.tolist(), batch.r0s.tolist())]     # SongEvicted before a write
         out[:] = 0
-        for k, (song, r0) in enumerate(zip(batch.songs.tolist(), batch.r0s.tolist())):
-            s = self.songs[song]
+        for k, (s, r0) in enumerate(rows):
+            song = batch.songs[k]
             if s['key'] != (batch.C, batch.T, batch.percussion):
                 raise ValueError(f'song {song} is of bucket {s["key"]}, the batch of {(batch.C, batch.T, batch.percussion)}')
             out[0, k] = (*s['pitched'], s['R'], r0)
@@ -429,9 +702,10 @@ class SongStore:
         target (the order of the plan's input slots)."""
         bucket = self.buckets[(batch.C, batch.T, batch.percussion)]
         views, out = bucket['views'], []
-        for song in batch.songs.tolist():
+        facts = [self._song(song) for song in batch.songs.tolist()]
+        for song, s in zip(batch.songs.tolist(), facts):
             if song not in views:
-                row = bucket['table'][self.songs[song]['row']]
+                row = bucket['table'][s['row']]
                 views[song] = [row[a:b] for a, b in bucket['fields']]
             out += views[song]
         return out

@@ -92,6 +92,52 @@ def fill_store(inputs, n_songs, store=None):
     return store
 
 
+class Rotation:
+    """The refresh schedule of `train(..., refresh_every=E, refresh_songs=M)`: `songs` yields what iter_sparse yields (a
+    SparseClip, or None for a song without pitched notes — skipped), `first_store` builds the ring from the first N usable
+    ones and `after(iteration)` admits the next M behind every E-th iteration.  It blocks on `songs`: the schedule is a
+    function of their order alone."""
+
+    def __init__(self, songs, every, count):
+        self.songs, self.every, self.count = songs, every, count
+        self.store, self.too_large, self.exhausted = None, 0, False
+
+    def take(self, n):
+        """The next `n` usable songs (fewer when the songs run out) that fit the ring, once there is one."""
+        out = []
+        while len(out) < n and not self.exhausted:
+            try:
+                clip = next(self.songs)
+            except StopIteration:
+                self.exhausted = True
+                break
+            if clip is None:
+                continue
+            if self.store is not None and max(clip.pitched_channels.count, 0 if clip.unpitched_channels is None
+                                              else clip.unpitched_channels.count) > self.store.capacity:
+                self.too_large += 1
+                continue
+            out.append(clip)
+        return out
+
+    def first_store(self, n_songs, records=None):
+        if records is not None:                   # (made first: `take` then leaves out the songs that cannot fit)
+            self.store = SongStore(device, capacity=int(records), resident=n_songs)
+        clips = self.take(n_songs)
+        if self.store is None:
+            total = max(sum(c.pitched_channels.count for c in clips),
+                        sum(c.unpitched_channels.count for c in clips if c.unpitched_channels is not None), 1)
+            self.store = SongStore(device, capacity=1 << (2 * total - 1).bit_length(), resident=n_songs)
+        self.store.admit(clips)
+        return self.store
+
+    def after(self, iteration):
+        if (iteration + 1) % self.every == 0 and not self.exhausted:
+            clips = self.take(self.count)
+            if clips:
+                self.store.admit(clips)
+
+
 class SmallInputStager:
     """The small host inputs of an iteration (mode, bpm, instrument features, used instruments) as ONE asynchronous upload
     through a ring of reusable pinned buffers, so that the loop thread allocates no pinned memory per iteration.  A buffer is
@@ -243,7 +289,8 @@ def evaluate_windows(model, store, bars, K, stride=None):
 def train(model, inputs, n_iterations=5000, iter_size=2, training_info_path='training.csv', save_path='snapshots/',
           save_interval=100, flush_every=20, progress=True, optimizer=None, fused=True, sparse_input=False,
           max_grad_norm=None, skip_nonfinite=False, save_optimizer=False, eval_inputs=None, eval_every=0, eval_clips=8,
-          eval_info_path='validation.csv', batch_clips=None, window_bars=16, store_songs=64, window_seed=0, eval_windows=None):
+          eval_info_path='validation.csv', batch_clips=None, window_bars=16, store_songs=64, window_seed=0, eval_windows=None,
+          refresh_every=None, refresh_songs=4, store_records=None):
     """`inputs`: iterator of (filename, get_input(...)) tuples, e.g. iter_parallel(iter_inputs(...)).
     fused=True runs a loop body as ONE C-ABI call (StyleTransferModel.train_iteration: same arithmetic, same gradients, no
     autograd graph); fused=False is the reference's own sequence model(...) -> get_total_loss -> backward.
@@ -273,13 +320,29 @@ def train(model, inputs, n_iterations=5000, iter_size=2, training_info_path='tra
     eval_windows = M (with batch_clips and eval_inputs; ValueError otherwise) makes validation follow: before the loop the next M
     usable songs of `eval_inputs` go into a second SongStore, and every due round is `evaluate_windows` over that store's fixed
     windows of `window_bars` bars in batches of `batch_clips` — the same windows every round, summed on the device.  `eval_clips`
-    is not used then; the CSV's `clips` column is the number of windows counted.  eval_windows=None: every path is as above."""
+    is not used then; the CSV's `clips` column is the number of windows counted.  eval_windows=None: every path is as above.
+    refresh_every = E (with batch_clips; ValueError otherwise) rotates the songs through a fixed ring on the device, so that the
+    batched loop trains on all of `inputs` in fixed device memory: the first `store_songs` = N usable songs are sparsified on
+    the host and admitted as one group to a SongStore(resident=N) whose pools hold `store_records` records each (default: twice
+    the larger pool's records of those N songs, rounded up to a power of two); after every E-th iteration — (iteration + 1) % E
+    == 0, behind optimizer.step() — the next `refresh_songs` = M usable songs are admitted (SongStore.admit: one upload, one
+    mst_store_admit launch) and the oldest leave.  No address moves, so train_windows' captured graph keeps replaying.  The
+    songs come from a prefetch thread (iter_sparse, as for sparse_input, stopped and joined the same way) and the loop WAITS
+    for its M songs: which songs are resident at which iteration depends on the order of `inputs` alone, never on timing.  A
+    song too large for the ring is skipped and counted (a warning at the end says how many); when `inputs` runs out, what it
+    still gave is admitted, refreshing stops and training goes on.  The ring's status words are read where the loop
+    synchronises anyway (the flush).  refresh_every=None: the loop, the append-only store included, is what it is without
+    this argument."""
     if optimizer is not None and (max_grad_norm is not None or skip_nonfinite):
         raise ValueError('max_grad_norm / skip_nonfinite configure the default optimizer; with optimizer= set them on that optimizer')
     if eval_windows is not None and (batch_clips is None or eval_inputs is None or int(eval_windows) < 1):
         raise ValueError('eval_windows = M >= 1 needs batch_clips (the shape and batch size of the windows) and eval_inputs (the '
                          'held-out songs)')
-    windows = None
+    if refresh_every is not None and (batch_clips is None or int(refresh_every) < 1 or int(refresh_songs) < 1 or
+                                      (store_records is not None and int(store_records) < 1)):
+        raise ValueError('refresh_every = E >= 1 needs batch_clips (the rotating store feeds windowed batches), refresh_songs >= 1 '
+                         'and, when given, store_records >= 1')
+    windows, feeder, rotation = None, None, None
     if batch_clips is not None:
         if not fused:
             raise ValueError('batch_clips needs fused=True: windowed batches run through StyleTransferModel.train_windows')
@@ -287,36 +350,56 @@ def train(model, inputs, n_iterations=5000, iter_size=2, training_info_path='tra
             raise ValueError('batch_clips, window_bars and store_songs must be at least 1')
         if iter_size != 1:
             warnings.warn(f'iter_size={iter_size} is ignored with batch_clips: the optimizer steps after every batch of {batch_clips} clips')
-        windows = (fill_store(inputs, int(store_songs)), np.random.default_rng(window_seed), int(batch_clips), int(window_bars))
-        if not len(windows[0]):
-            raise ValueError('batch_clips: `inputs` held no usable song')
-    eval_store = None
-    if eval_windows is not None:
-        eval_store = fill_store(eval_inputs, int(eval_windows))
-        if not len(eval_store):
-            raise ValueError('eval_windows: `eval_inputs` held no usable song')
-    feeder = None
+        if refresh_every is None:
+            store = fill_store(inputs, int(store_songs))
+        else:
+            feeder = ParallelIterable(iter_sparse(inputs))
+            try:
+                rotation = Rotation(iter(feeder), int(refresh_every), int(refresh_songs))
+                store = rotation.first_store(int(store_songs), store_records)
+            except BaseException:
+                feeder.stop(timeout=5.)
+                raise
+        windows = (store, np.random.default_rng(window_seed), int(batch_clips), int(window_bars))
     if sparse_input and windows is None:
         feeder = ParallelIterable(iter_sparse(inputs))
         inputs = iter(feeder)
     try:
+        if windows is not None and not len(windows[0]):
+            raise ValueError('batch_clips: `inputs` held no usable song')
+        eval_store = None
+        if eval_windows is not None:
+            eval_store = fill_store(eval_inputs, int(eval_windows))
+            if not len(eval_store):
+                raise ValueError('eval_windows: `eval_inputs` held no usable song')
         return _train_loop(model, inputs, n_iterations, iter_size, training_info_path, save_path, save_interval, flush_every,
                            progress, optimizer, fused, sparse_input, max_grad_norm, skip_nonfinite, save_optimizer,
                            eval_inputs if eval_every and eval_every > 0 else None, eval_every, eval_clips, eval_info_path, windows,
-                           eval_store)
+                           eval_store, rotation)
     finally:
         if feeder is not None:
             feeder.stop(timeout=5.)
+        if rotation is not None and rotation.too_large:
+            warnings.warn(f'refresh_every: {rotation.too_large} songs hold more records than the ring (store_records) and were skipped')
 
 
 def _train_loop(model, inputs, n_iterations, iter_size, training_info_path, save_path, save_interval, flush_every, progress,
                 optimizer, fused, sparse_input, max_grad_norm=None, skip_nonfinite=False, save_optimizer=False,
-                eval_inputs=None, eval_every=0, eval_clips=8, eval_info_path='validation.csv', windows=None, eval_store=None):
+                eval_inputs=None, eval_every=0, eval_clips=8, eval_info_path='validation.csv', windows=None, eval_store=None,
+                rotation=None):
     optimizer = optimizer or FusedAdam(model, lr=.01, step_size=200, gamma=.9, max_grad_norm=max_grad_norm,
                                        skip_nonfinite=skip_nonfinite)
     optimizer.zero_grad()
     pbar = ProgressBar(n_iterations) if progress else None
-    log = LossLog(training_info_path, pbar, flush_every, health=getattr(model, 'check_device_status', None),
+    health = getattr(model, 'check_device_status', None)
+    if rotation is not None:
+        model_health = health
+
+        def health():                     # at the flush, where the loop synchronises anyway
+            if model_health is not None:
+                model_health()
+            rotation.store.check()
+    log = LossLog(training_info_path, pbar, flush_every, health=health,
                   tolerate_nan=bool(getattr(optimizer, 'skip_nonfinite', False)), guard_stats=getattr(optimizer, 'guard_stats', None))
     stager = SmallInputStager(device) if sparse_input and windows is None else None
     for iteration in range(n_iterations):
@@ -328,6 +411,8 @@ def _train_loop(model, inputs, n_iterations, iter_size, training_info_path, save
             packed = model.train_windows(store, batch).mean(0)      # one row per iteration: the leaves averaged over the K clips
             log.add(iteration, packed)
             optimizer.step()                      # K clips have accumulated: K takes iter_size's place
+            if rotation is not None:
+                rotation.after(iteration)
             _after_iteration(model, optimizer, log, pbar, iteration, eval_inputs, eval_every, eval_clips, eval_info_path,
                              sparse_input, save_interval, save_path, save_optimizer,
                              None if eval_store is None else (eval_store, window_bars, batch_clips))

@@ -22,9 +22,15 @@ and their spread).
                interleaved with transfer_windows at the same K on the same windows (the path without the bank: the three new
                launches are the difference) and with the per-window Python surface with select_instruments on the host in the
                loop; and, under device events, mst_style_put, mst_style_mix and mst_info_decide at 64 clips.
+  --rotate     times the rotating store instead: the loop sample -> train_windows -> step on a ring SongStore(resident=--songs)
+               that admits M pre-sparsified songs after every E-th iteration, (E, M) = (16, 4) and (4, 4), for every K of
+               --clips, alternating in one process with the same loop without refresh (the yardstick: train_windows as it
+               was, on the same store, so that one captured graph serves both legs); reported are both rates, their ratio and the host time of `admit` on the loop thread; and, under
+               device events, one refresh of four songs: the mst_store_admit launch against the 5 x 4 separate copies `add`
+               makes for the same songs and against a device-to-device copy of the same bytes.
 One JSON line per measurement; --out writes them all to a file.
 Usage on the GPU box: python tools/window_rate.py [--songs 16] [--iters 150] [--runs 5] [--one-clip] [--kernels] [--eval
-                      [--eval-stride S]] [--transfer] [--styles] [--out FILE]"""
+                      [--eval-stride S]] [--transfer] [--styles] [--rotate] [--out FILE]"""
 import argparse
 import json
 import os
@@ -468,6 +474,101 @@ def style_kernels(model, store, K, entries=8, reps=50):
     return res
 
 
+def rotate_legs(model, opt, ring, fresh, K, E, M, iters, runs, warmup=4):
+    """Clip-iterations per second of the loop with and without refresh, alternated; `fresh` is an endless source of
+    pre-sparsified songs."""
+    rngs = {True: np.random.default_rng(0), False: np.random.default_rng(0)}
+    spent = []
+
+    def loop(n, refresh):
+        rng = rngs[refresh]
+        for i in range(n):
+            model.train_windows(ring, ring.sample(rng, K, BARS))
+            opt.step()
+            if refresh and (i + 1) % E == 0:
+                t0 = time.perf_counter()
+                ring.admit([next(fresh) for _ in range(M)])
+                spent.append(time.perf_counter() - t0)
+    for refresh in (False, True):
+        loop(max(warmup, E), refresh)                     # eager, capture + replay, replays; the staging buffers of admit
+    torch.cuda.synchronize()
+    spent.clear()
+    rates = {False: [], True: []}
+    for _ in range(runs):
+        for refresh in (False, True):                     # alternated
+            t0 = time.perf_counter()
+            loop(iters, refresh)
+            torch.cuda.synchronize()
+            rates[refresh].append(K * iters / (time.perf_counter() - t0))
+    ring.check()
+    model.check_device_status()
+    ratio = statistics.median(rates[True]) / statistics.median(rates[False])
+    return [dict(what='train_windows + FusedAdam.step, no refresh', K=K, bars=BARS, unit='clip-iterations/s', **spread(rates[False])),
+            dict(what=f'the same with SongStore.admit of {M} songs after every {E}th iteration', K=K, E=E, M=M, bars=BARS,
+                 unit='clip-iterations/s', ratio_to_no_refresh=ratio, admit_host_us=spread([t * 1e6 for t in spent]), **spread(rates[True]))]
+
+
+def rotate_kernels(ring, clips, reps=50):
+    """Microseconds under device events of one refresh of `clips`: the mst_store_admit launch alone (the blob already staged),
+    the whole `admit` (pack, upload, launch), the separate copies of `add` into an append-only store, and one device-to-device
+    copy of the same bytes."""
+    from style import _native
+    from style.data import SongStore
+    native, dev = _native.get(), ring.device
+    ring.admit(clips)
+    torch.cuda.synchronize()
+    ring.check()
+    key = ring.songs[ring.resident()[-1]]['key']
+    dsts = _native.AdmitDsts([ring.pools[5].cells, ring.pools[5].feats, ring.pools[2].cells, ring.pools[2].feats, ring.buckets[key]['table']])
+    words = sum(c.pitched_channels.count * 6 + c.unpitched_channels.count * 3 for c in clips) + len(clips) * ring.buckets[key]['table'].shape[1]
+    stream = _native.current_stream(dev)
+    src, dst = torch.zeros(words, dtype=torch.int32, device=dev), torch.zeros(words, dtype=torch.int32, device=dev)
+    plain = SongStore(dev, capacity=1 << 22)
+
+    def adds():
+        for c in clips:
+            plain.add(c)
+    calls = (('mst_store_admit launch', lambda: native.store_admit(ring._blob, ring._blob.numel(), ring._max_segments, dsts, ring._status[0], stream)),
+             ('SongStore.admit (pack, upload, launch)', lambda: ring.admit(clips)),
+             (f'SongStore.add x {len(clips)} (append-only: {5 * len(clips)} copies)', adds),
+             ('device-to-device copy of the same bytes', lambda: dst.copy_(src)))
+    res = []
+    for name, fn in calls + calls:                         # alternated
+        fn()
+        torch.cuda.synchronize()
+        times, host = [], []
+        for _ in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            a.record()
+            fn()
+            b.record()
+            host.append((time.perf_counter() - t0) * 1e6)
+            b.synchronize()
+            times.append(a.elapsed_time(b) * 1e3)
+        res.append(dict(what=name, songs=len(clips), bytes=4 * words, unit='us', host_us=spread(host),
+                        gb_per_s=4 * words / (statistics.median(times) * 1e-6) / 1e9, **spread(times)))
+    ring.check()
+    return res
+
+
+def rotate(model, opt, songs, clips, iters, runs):
+    from style.train import Rotation, iter_sparse
+    resident = [c for c in iter_sparse(iter(songs)) if c is not None]
+    more = [c for c in iter_sparse(iter(synth_songs(16, seed=1))) if c is not None]
+
+    def endless():
+        while True:
+            yield from more
+    results = []
+    for K in clips:
+        for E, M in ((16, 4), (4, 4)):
+            ring = Rotation(iter(resident), E, M).first_store(len(resident))
+            results += rotate_legs(model, opt, ring, endless(), K, E, M, iters, runs)
+    results += rotate_kernels(ring, more[:4])
+    return results
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--songs', type=int, default=16)
@@ -480,6 +581,7 @@ def main():
     ap.add_argument('--eval-stride', type=int, default=None)
     ap.add_argument('--transfer', action='store_true')
     ap.add_argument('--styles', action='store_true')
+    ap.add_argument('--rotate', action='store_true')
     ap.add_argument('--out')
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -505,7 +607,9 @@ def main():
         results += style_kernels(model, store, 64)
     opt = FusedAdam(model)
     opt.zero_grad()
-    for K in [] if args.eval or args.transfer or args.styles else args.clips:
+    if args.rotate:
+        results += rotate(model, opt, songs, args.clips, args.iters, args.runs)
+    for K in [] if args.eval or args.transfer or args.styles or args.rotate else args.clips:
         results.append(windowed(model, opt, store, K, args.iters, args.runs))
     if args.one_clip:
         results.append(one_clip(build_model(seed=108), songs, args.iters * 16, args.runs))
