@@ -540,6 +540,49 @@ int32_t mst_info_decide(const float* instruments_pred, const float* mode_pred, c
                         float* instr, float* mode, float* bpm, int64_t out_stride,
                         int32_t* decisions /* n_clips x (channels + 2) */, mst_stream stream);
 
+/* ---- style search: which rows of a bank resemble a style.  The cosines of n_queries queries (len floats each, query_stride
+ * floats apart) against the rows of a bank (bank_rows runs of len floats, bank_stride floats apart) and, per query, the k best
+ * rows.  No reference counterpart: the reference keeps no library of styles.  Two launches — scores and the k best of every slab
+ * of MST_SEARCH_SLAB rows, then a merge per query — both enqueue-only on `stream` (no allocation, no host synchronisation,
+ * capturable as a single chain), without atomics and without a workgroup waiting for another: the same bits on every run.  Every
+ * index array is DEVICE memory, read on the device: a captured call serves other queries, another n_live and other groups.
+ *
+ * Arithmetic, for query q and row r:
+ *   dot(q, r)   acc = +0.0f; for i = 0 ... len - 1 in ascending order: acc = fmaf(q[i], r[i], acc).  One fp32 chain per pair,
+ *               no k-split: what a k-ordered sequence of v_mfma_f32_16x16x4_f32 gives, bit for bit.
+ *   nq, nr      dot(q, q) and dot(r, r), the same chain.
+ *   score       dot(q, r) / (sqrtf(nq) * sqrtf(nr)): two correctly rounded roots, their product and the quotient, each rounded
+ *               to fp32 on its own.
+ * The score of a pair depends on the len floats of q and of r only: not on where the row sits in the bank, on which slab or
+ * query tile it falls in, nor on n_queries, bank_rows or k.
+ *
+ * Ranking.  Row r is RANKABLE for query q when r < min(*n_live, bank_rows) (n_live: one DEVICE int32, NULL = bank_rows, a
+ * negative value counts as 0); and, where groups, exclude and exclude[q] >= 0 are all given, groups[r] != exclude[q]; and the
+ * score is not NaN (a zero row or a zero query gives 0 / 0 and drops out by itself).  The rankable rows are ordered by
+ * order * score descending (order = +1: the nearest first, -1: the farthest first), compared as floats, equal keys by ascending
+ * row; rows[q * k + j] and scores[q * k + j] hold the j-th of that order, positions past the last rankable row hold row -1 and
+ * score 0x7fc00000.  So `rows` can be handed to mst_style_mix as its idx, with offsets[q] = q * k.  Every word of rows and
+ * scores is written exactly once and nothing else is written, scratch aside (mst_style_search_scratch_bytes(bank_rows,
+ * n_queries, k) bytes, 8-byte aligned; <= 0 on arguments mst_style_search refuses); the bank, groups, queries and exclude are
+ * read only.  Rows that start on 16-byte boundaries (bank 16-byte aligned, bank_stride a multiple of 4; the queries likewise)
+ * are read 16 bytes per lane, others float by float: the same bits.  Rows at and behind bank_rows are never read; a slab
+ * wholly behind *n_live is not read either.
+ * MST_ERR_ARG, and nothing is launched: a null bank, queries, rows, scores or scratch; bank_rows, n_queries or len < 1;
+ * n_queries > 4096; len > 4096; k outside [1, MST_SEARCH_MAX_K]; order not +1 or -1; a negative stride; a float or int pointer
+ * not 4-byte aligned; scratch not 8-byte aligned; rows / scores intersecting each other, the bank's rows or the queries, or these
+ * ranges not representable; exclude given without groups; more than 2^31 - 1 workgroups (slabs x tiles of 64 queries). */
+#define MST_SEARCH_MAX_K 16
+#define MST_SEARCH_SLAB 64
+int64_t mst_style_search_scratch_bytes(int32_t bank_rows, int32_t n_queries, int32_t k);
+int32_t mst_style_search(const float* bank, int32_t bank_rows, int64_t bank_stride,
+                         const int32_t* n_live /* DEVICE, one int32, or NULL = bank_rows */,
+                         const int32_t* groups /* DEVICE int32[bank_rows] or NULL */,
+                         const float* queries, int32_t n_queries, int64_t query_stride,
+                         const int32_t* exclude /* DEVICE int32[n_queries] or NULL */,
+                         int64_t len, int32_t k, int32_t order /* +1 nearest, -1 farthest */,
+                         int32_t* rows /* n_queries x k */, float* scores /* n_queries x k */,
+                         void* scratch, mst_stream stream);
+
 /* ---- instrumentation (bench.py only; synchronises on HIP events, never used for training):
  * average duration of every launch step of a pass, with its algorithmic FLOPs and bytes.
  * kind: 0 gemm, 1 gather, 2 segment-reduce, 3/4 lstm fwd/bwd, 5/6 combine fwd/bwd, 7/8 melody notes, 9/10 applier notes,

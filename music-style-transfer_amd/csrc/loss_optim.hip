@@ -2058,3 +2058,253 @@ extern "C" int32_t mst_info_decide(const float* instruments_pred, const float* m
                        pred_stride, a, live, instr, mode, bpm, out_stride, decisions);
     return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
 }
+
+// ------------------------------------------------------------------ style search (mst_style_search)
+// Which rows of a bank resemble a style: the cosines of a batch of queries against every row and the k best per query, in two
+// launches.  (a) One workgroup per SS_SLAB rows and SS_QT queries: k-tiles of SS_KT floats of both are staged in LDS (the bank is
+// read once per query tile), wave w owns rows [16 w, 16 w + 16) of the slab against all SS_QT queries, four 16x16x4 f32 MFMA
+// accumulators, every k-tile visited in order — one fmaf chain per (query, row), no k-split; the norms are the same chain walked
+// by one lane per row over the staged values.  Zeros staged behind `len` add nothing to a chain (fmaf(0, 0, acc) = acc for the
+// acc >= +0 of a norm and for every acc of a dot but a -0 that only an underflowed product can leave).  The scores then go
+// through LDS to a counting rank per query — lane = row, 64 comparisons whatever the values, a total order — and the slab's k best
+// go to scratch.  (b) One workgroup per query picks the best candidate below the previous pick, k times.
+// No atomics, no workgroup waits for another.
+#define SS_THREADS 256
+#define SS_SLAB MST_SEARCH_SLAB
+#define SS_QT 64             // queries of a workgroup
+#define SS_KT 32             // floats of a k-tile
+#define SS_LD (SS_KT + 4)    // row stride of a staged tile: lane l reads [l & 15][4 kk + (l >> 4)], 36 r + c hits 64 different banks
+#define SS_SD (SS_SLAB + 4)  // row stride of the score image
+static_assert(SS_SLAB == 64 && SS_QT == 64 && SS_THREADS == 256, "style_search_kernel: one lane per row, 16 rows per wave");
+
+typedef uint32_t ss_u4 __attribute__((ext_vector_type(4)));
+
+// the order of the ranking as unsigned integers: larger = earlier.  0 is no float's key (the smallest is -inf's, 0x007fffff),
+// so it marks a row that is not rankable; -0 and +0 are one key, as they are equal as floats.
+__device__ __forceinline__ uint32_t search_key(float score, int order) {
+    uint32_t u = __float_as_uint(order > 0 ? score : -score);
+    if (u == 0x80000000u) u = 0u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// this lane's two 16-byte pieces of a 64 x SS_KT tile of rows [first, first + n_rows) of `base`, floats [i0, i0 + SS_KT): piece
+// s = tid + 256 h is floats [4 (s & 7), + 4) of row s >> 3.  Nothing outside the rows' `len` floats is read: zeros instead.
+template <bool VEC>
+__device__ __forceinline__ void search_fetch(const float* base, int64_t stride, int64_t first, int n_rows, int i0, int len, int tid,
+                                             roll_f4 (&v)[2]) {
+    const MST_GLOBAL_AS float* g = (const MST_GLOBAL_AS float*)base;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int s = tid + SS_THREADS * h, r = s >> 3, i = i0 + 4 * (s & 7);
+        roll_f4 x = {0.f, 0.f, 0.f, 0.f};
+        if (r < n_rows && i < len) {
+            const MST_GLOBAL_AS float* p = g + ((first + r) * stride + i);
+            if (VEC && i + 4 <= len) {
+                x = *reinterpret_cast<const MST_GLOBAL_AS roll_f4*>(p);
+            } else {
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    if (i + c < len) x[c] = p[c];
+            }
+        }
+        v[h] = x;
+    }
+}
+
+__device__ __forceinline__ void search_stage(float* tile, int tid, const roll_f4 (&v)[2]) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int s = tid + SS_THREADS * h;
+        *reinterpret_cast<roll_f4*>(tile + (s >> 3) * SS_LD + 4 * (s & 7)) = v[h];
+    }
+}
+
+template <bool VB, bool VQ>
+__global__ __launch_bounds__(SS_THREADS) void style_search_kernel(const float* bank, int bank_rows, int64_t bank_stride, const int32_t* n_live,
+                                                                  const int32_t* groups, const float* queries, int n_queries,
+                                                                  int64_t query_stride, const int32_t* exclude, int len, int k, int order,
+                                                                  int slabs, float* sc_scores, int32_t* sc_rows) {
+    // the two staged tiles (2 x 64 x SS_LD floats) while the scores are summed, then the keys and the scores (2 x 64 x SS_SD)
+    __shared__ __attribute__((aligned(16))) float sm[2 * SS_QT * SS_SD];
+    __shared__ float s_nr[SS_SLAB], s_nq[SS_QT];
+    __shared__ int32_t s_grp[SS_SLAB], s_ex[SS_QT];
+    float* t_r = sm;
+    float* t_q = sm + SS_SLAB * SS_LD;
+    uint32_t* s_key = reinterpret_cast<uint32_t*>(sm);
+    float* s_sc = sm + SS_QT * SS_SD;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int slab = blockIdx.x % slabs, q0 = (blockIdx.x / slabs) * SS_QT;
+    const int row0 = slab * SS_SLAB;
+    const int nq = n_queries - q0 < SS_QT ? n_queries - q0 : SS_QT;
+    const int nr = bank_rows - row0 < SS_SLAB ? bank_rows - row0 : SS_SLAB;
+    int live = n_live ? MST_UNIFORM(n_live[0]) : bank_rows;
+    live = live < 0 ? 0 : live > bank_rows ? bank_rows : live;
+    if (row0 >= live) {                                         // (workgroup-uniform) a slab behind the live rows is not read
+        for (int e = tid; e < nq * k; e += SS_THREADS) {
+            const int64_t at = ((int64_t)(q0 + e / k) * slabs + slab) * k + e % k;
+            sc_rows[at] = -1;
+            sc_scores[at] = __uint_as_float(0x7fc00000u);
+        }
+        return;
+    }
+    if (tid < SS_SLAB) s_grp[tid] = (groups && tid < nr) ? groups[row0 + tid] : -1;
+    else if (tid < SS_SLAB + SS_QT) s_ex[tid - SS_SLAB] = (groups && exclude && tid - SS_SLAB < nq) ? exclude[q0 + tid - SS_SLAB] : -1;
+
+    roll_f4 acc[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n) acc[n] = roll_f4{0.f, 0.f, 0.f, 0.f};
+    float norm = 0.f;                                           // tid < 64: of row tid; tid < 128: of query tid - 64
+    const float* n_at = tid < SS_SLAB ? t_r + tid * SS_LD : t_q + (tid - SS_SLAB) * SS_LD;
+    const float* a_at = t_r + (wave * 16 + (lane & 15)) * SS_LD + (lane >> 4);
+    const float* b_at = t_q + (lane & 15) * SS_LD + (lane >> 4);
+    roll_f4 vr[2], vq[2];
+    search_fetch<VB>(bank, bank_stride, row0, nr, 0, len, tid, vr);
+    search_fetch<VQ>(queries, query_stride, q0, nq, 0, len, tid, vq);
+    for (int i0 = 0; i0 < len; i0 += SS_KT) {                   // (workgroup-uniform)
+        search_stage(t_r, tid, vr);
+        search_stage(t_q, tid, vq);
+        __syncthreads();
+        if (i0 + SS_KT < len) {                                 // the next k-tile travels while this one is summed
+            search_fetch<VB>(bank, bank_stride, row0, nr, i0 + SS_KT, len, tid, vr);
+            search_fetch<VQ>(queries, query_stride, q0, nq, i0 + SS_KT, len, tid, vq);
+        }
+        if (tid < SS_SLAB + SS_QT) {
+#pragma unroll
+            for (int i4 = 0; i4 < SS_KT / 4; ++i4) {
+                const roll_f4 x = *reinterpret_cast<const roll_f4*>(n_at + 4 * i4);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) norm = __builtin_fmaf(x[c], x[c], norm);
+            }
+        }
+#pragma unroll
+        for (int kk = 0; kk < SS_KT / 4; ++kk) {
+            const float a = a_at[4 * kk];
+#pragma unroll
+            for (int n = 0; n < 4; ++n)
+                if (n * 16 < nq)                                // (workgroup-uniform)
+                    acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b_at[n * 16 * SS_LD + 4 * kk], acc[n], 0, 0, 0);
+        }
+        __syncthreads();                                        // the tiles are rewritten by the next stretch, or by the keys
+    }
+    if (tid < SS_SLAB) s_nr[tid] = norm;
+    else if (tid < SS_SLAB + SS_QT) s_nq[tid - SS_SLAB] = norm;
+    __syncthreads();
+    // D[row = 4 (lane >> 4) + j][col = lane & 15] of accumulator n is (row 16 wave + ..., query 16 n + col)
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+        const int q = n * 16 + (lane & 15);
+        const float root_q = sqrtf(s_nq[q]);
+        const int ex = s_ex[q];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int r = wave * 16 + (lane >> 4) * 4 + j;
+            const float root_r = sqrtf(s_nr[r]);
+            const float den = root_q * root_r;
+            const float score = acc[n][j] / den;
+            const bool rankable = row0 + r < live && !(ex >= 0 && s_grp[r] == ex) && score == score;
+            s_key[q * SS_SD + r] = rankable ? search_key(score, order) : 0u;
+            s_sc[q * SS_SD + r] = score;
+        }
+    }
+    __syncthreads();
+    // wave w ranks queries [16 w, 16 w + 16); lane = row.  (key, row) is different for every lane, so the ranks are a permutation
+    // of 0 .. 63 and every position below k has exactly one writer: a rankable row, or -1 / NaN from one that is not.
+    for (int qq = 0; qq < 16; ++qq) {
+        const int q = wave * 16 + qq;
+        if (q >= nq) break;                                     // (wave-uniform)
+        const uint32_t own = s_key[q * SS_SD + lane];
+        int rank = 0;
+#pragma unroll
+        for (int i4 = 0; i4 < SS_SLAB / 4; ++i4) {
+            const ss_u4 o = *reinterpret_cast<const ss_u4*>(s_key + q * SS_SD + 4 * i4);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) rank += (o[c] > own || (o[c] == own && 4 * i4 + c < lane)) ? 1 : 0;
+        }
+        if (rank < k) {
+            const int64_t at = ((int64_t)(q0 + q) * slabs + slab) * k + rank;
+            sc_rows[at] = own ? row0 + lane : -1;
+            sc_scores[at] = own ? s_sc[q * SS_SD + lane] : __uint_as_float(0x7fc00000u);
+        }
+    }
+}
+
+// One workgroup per query over its m = slabs x k candidates: pick j is the largest (key, lowest row) below pick j - 1.  The
+// 64-bit keys of rankable candidates are all different (the rows are), so "below the previous" removes exactly the picks made.
+__global__ __launch_bounds__(SS_THREADS) void style_search_merge_kernel(const float* sc_scores, const int32_t* sc_rows, int m, int k, int order,
+                                                                        int32_t* rows, float* scores) {
+    __shared__ uint64_t s_best[SS_THREADS];
+    const int tid = threadIdx.x, q = blockIdx.x;
+    const int64_t base = (int64_t)q * m;
+    uint64_t prev = ~(uint64_t)0;
+    for (int j = 0; j < k; ++j) {                               // (workgroup-uniform)
+        uint64_t best = 0;
+        float best_score = 0.f;
+        for (int c = tid; c < m; c += SS_THREADS) {
+            const int32_t r = sc_rows[base + c];
+            if (r < 0) continue;
+            const float s = sc_scores[base + c];
+            const uint64_t key = ((uint64_t)search_key(s, order) << 32) | (uint32_t)(0x7fffffff - r);
+            if (key < prev && key > best) best = key, best_score = s;
+        }
+        s_best[tid] = best;
+        __syncthreads();
+        for (int s = SS_THREADS / 2; s > 0; s >>= 1) {
+            if (tid < s && s_best[tid + s] > s_best[tid]) s_best[tid] = s_best[tid + s];
+            __syncthreads();
+        }
+        const uint64_t win = s_best[0];
+        __syncthreads();                                        // s_best is rewritten by the next pick
+        if (win == 0) {
+            if (tid == 0) {
+                rows[(int64_t)q * k + j] = -1;
+                scores[(int64_t)q * k + j] = __uint_as_float(0x7fc00000u);
+            }
+        } else if (best == win) {
+            rows[(int64_t)q * k + j] = 0x7fffffff - (int32_t)(uint32_t)win;
+            scores[(int64_t)q * k + j] = best_score;
+        }
+        prev = win;
+    }
+}
+
+extern "C" int64_t mst_style_search_scratch_bytes(int32_t bank_rows, int32_t n_queries, int32_t k) {
+    if (bank_rows < 1 || n_queries < 1 || n_queries > 4096 || k < 1 || k > MST_SEARCH_MAX_K) return 0;
+    const int64_t slabs = ((int64_t)bank_rows + SS_SLAB - 1) / SS_SLAB;
+    return 8 * slabs * n_queries * k;
+}
+
+extern "C" int32_t mst_style_search(const float* bank, int32_t bank_rows, int64_t bank_stride, const int32_t* n_live, const int32_t* groups,
+                                    const float* queries, int32_t n_queries, int64_t query_stride, const int32_t* exclude, int64_t len,
+                                    int32_t k, int32_t order, int32_t* rows, float* scores, void* scratch, mst_stream stream) {
+    if (!bank || !queries || !rows || !scores || !scratch || bank_rows < 1 || n_queries < 1 || n_queries > 4096 || len < 1 || len > 4096 ||
+        k < 1 || k > MST_SEARCH_MAX_K || (order != 1 && order != -1) || bank_stride < 0 || query_stride < 0 || (exclude && !groups) ||
+        ((uintptr_t)scratch & 7))
+        return MST_ERR_ARG;
+    const void* all[] = {bank, queries, rows, scores, n_live, groups, exclude};
+    for (const void* p : all)
+        if ((uintptr_t)p & 3) return MST_ERR_ARG;
+    int64_t bank_span, query_span;
+    if (!span_floats(bank_rows, bank_stride, len, &bank_span) || !span_floats(n_queries, query_stride, len, &query_span)) return MST_ERR_ARG;
+    const int64_t out = (int64_t)n_queries * k;
+    if (floats_intersect(rows, out, scores, out) || floats_intersect(rows, out, bank, bank_span) || floats_intersect(rows, out, queries, query_span) ||
+        floats_intersect(scores, out, bank, bank_span) || floats_intersect(scores, out, queries, query_span))
+        return MST_ERR_ARG;
+    const int64_t slabs = ((int64_t)bank_rows + SS_SLAB - 1) / SS_SLAB, tiles = (n_queries + SS_QT - 1) / SS_QT;
+    if (slabs * tiles > 0x7fffffff) return MST_ERR_ARG;
+    float* sc_scores = (float*)scratch;
+    int32_t* sc_rows = (int32_t*)(sc_scores + slabs * n_queries * k);
+    const dim3 grid((unsigned)(slabs * tiles)), block(SS_THREADS);
+    const bool vb = !((uintptr_t)bank & 15) && bank_stride % 4 == 0, vq = !((uintptr_t)queries & 15) && query_stride % 4 == 0;
+#define SS_LAUNCH(VB, VQ)                                                                                                              \
+    hipLaunchKernelGGL((style_search_kernel<VB, VQ>), grid, block, 0, (hipStream_t)stream, bank, (int)bank_rows, bank_stride, n_live, groups, \
+                       queries, (int)n_queries, query_stride, exclude, (int)len, (int)k, (int)order, (int)slabs, sc_scores, sc_rows)
+    if (vb && vq) SS_LAUNCH(true, true);
+    else if (vb) SS_LAUNCH(true, false);
+    else if (vq) SS_LAUNCH(false, true);
+    else SS_LAUNCH(false, false);
+#undef SS_LAUNCH
+    if (hipGetLastError() != hipSuccess) return MST_ERR_LAUNCH;
+    hipLaunchKernelGGL(style_search_merge_kernel, dim3((unsigned)n_queries), block, 0, (hipStream_t)stream, sc_scores, sc_rows,
+                       (int)(slabs * k), (int)k, (int)order, rows, scores);
+    return hipGetLastError() == hipSuccess ? MST_OK : MST_ERR_LAUNCH;
+}

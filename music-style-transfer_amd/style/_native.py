@@ -50,6 +50,8 @@ METRIC_WORDS = 8                    # mst_amd.h MST_METRIC_WORDS: doubles per re
 ROW_FIELDS = 8                      # mst_amd.h MST_ROW_FIELDS: pieces of a table row one mst_window_inputs call places
 STYLE_SUM_WORDS = 8                 # mst_amd.h MST_STYLE_SUM_WORDS: doubles per clip of mst_style_sums
 EVAL_ACC_WORDS = 41                 # mst_amd.h MST_EVAL_ACC_WORDS: doubles of a round's running sum (mst_eval_accumulate)
+SEARCH_MAX_K = 16                   # mst_amd.h MST_SEARCH_MAX_K: the most neighbours per query of mst_style_search
+SEARCH_SLAB = 64                    # mst_amd.h MST_SEARCH_SLAB: rows of the bank one workgroup of mst_style_search owns
 ADMIT_DSTS = 16                     # mst_amd.h MST_ADMIT_DSTS: destinations one mst_store_admit call names
 SEGMENT_WORDS = 4                   # mst_amd.h mst_segment: int32 words per segment of mst_store_admit (dst, dst_off, src_off, words)
 
@@ -172,6 +174,9 @@ _SIGS = {
     'mst_style_mix': (C.c_int32, [_P, C.c_int32, C.c_int64, _P, _P, _P, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int64, _P]),
     'mst_info_decide': (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P,
                                     C.c_int64, _P, _P]),
+    'mst_style_search_scratch_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    'mst_style_search': (C.c_int32, [_P, C.c_int32, C.c_int64, _P, _P, _P, C.c_int32, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P,
+                                     _P, _P]),
     'mst_roll_metrics_scratch_bytes': (C.c_int64, [C.c_int64, C.c_int64]),
     'mst_roll_metrics': (C.c_int32, [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P]),
     'mst_eval_scratch_bytes': (C.c_int64, [_P]),
@@ -354,6 +359,24 @@ class Native:
         check(self.lib.mst_info_decide(addr(instruments_pred), addr(mode_pred), addr(bpm_pred), int(pred_stride), int(n_logits), groups,
                                        int(n_groups), int(channels), int(n_clips), int(bool(pool)), addr(live), addr(instr), addr(mode),
                                        addr(bpm), int(out_stride), addr(decisions), stream), 'mst_info_decide')
+
+    def style_search_scratch_bytes(self, bank_rows, n_queries, k):
+        n = self.lib.mst_style_search_scratch_bytes(int(bank_rows), int(n_queries), int(k))
+        if n <= 0:
+            raise MstError(f'mst_style_search_scratch_bytes: bad arguments ({bank_rows} rows, {n_queries} queries, k = {k})')
+        return n
+
+    def style_search(self, bank, bank_rows, bank_stride, n_live, groups, queries, n_queries, query_stride, exclude, length, k, order,
+                     rows, scores, scratch, stream=None):
+        """mst_style_search: per query the `k` rows of the bank with the largest (order = +1) or smallest (-1) cosine, into
+        `rows` (int32, n_queries x k; -1 past the last rankable row) and `scores` (float32, likewise; NaN there).  `n_live` (one
+        int32), `groups` (int32 per row) and `exclude` (int32 per query: rows of that group are skipped, -1 skips none) are read
+        on the device and may be None.  `scratch`: style_search_scratch_bytes bytes, 8-byte aligned.  Tensors on one device or
+        raw addresses.  Two launches, enqueue-only."""
+        addr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()
+        check(self.lib.mst_style_search(addr(bank), int(bank_rows), int(bank_stride), addr(n_live), addr(groups), addr(queries),
+                                        int(n_queries), int(query_stride), addr(exclude), int(length), int(k), int(order), addr(rows),
+                                        addr(scores), addr(scratch), stream), 'mst_style_search')
 
     def roll_metrics_scratch_bytes(self, n_groups, group_cells):
         n = self.lib.mst_roll_metrics_scratch_bytes(int(n_groups), int(group_cells))

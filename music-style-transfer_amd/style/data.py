@@ -721,14 +721,20 @@ class StyleBank:
 
     A style to render with is a list of ENTRIES `(row, weight)`: `row(r)` is one stored style, `song(s)` the mean of a song's
     windows, `blend([...])` a weighted sum of such, and `StyleBank.mix` packs K of them as the CSR arrays mst_style_mix reads.
-    Weights are float32 and products of them are rounded to float32, the arithmetic of the device."""
+    Weights are float32 and products of them are rounded to float32, the arithmetic of the device.
+
+    Every row has a GROUP, the ordinal of its song in `by_song`'s insertion order, so that a search can leave out a song's own
+    rows (mst_style_search's groups / exclude).  The host keeps the groups as rows are taken; the device copy `groups` (int32, one
+    per row of the capacity, sized and moved with `rows`) is refreshed at the next search, never during a capture."""
 
     def __init__(self, style_size, device=device, capacity=64):
         self.style_size, self.device = int(style_size), torch.device(device)
         if self.style_size < 1 or int(capacity) < 1:
             raise ValueError('StyleBank: style_size and capacity must be at least 1')
         self.rows = torch.zeros(int(capacity), self.style_size, dtype=torch.float32, device=self.device)
+        self.groups = torch.full((int(capacity),), -1, dtype=torch.int32, device=self.device)
         self.used, self.provenance, self.by_song = 0, [], {}
+        self._groups, self._group_of, self._groups_on_device, self._search = [], {}, 0, {}
 
     def __len__(self):
         return self.used
@@ -748,12 +754,15 @@ class StyleBank:
             rows = self.rows.new_zeros(capacity, self.style_size)
             rows[:self.used].copy_(self.rows[:self.used])
             self.rows = rows                              # (the old one is recycled in stream order)
+            self.groups = self.groups.new_full((capacity,), -1)
+            self._groups_on_device = 0
 
     def take(self, song, r0, bars):
         """Name the next free row as the style of bars [r0, r0 + bars) of `song`; returns the row for whoever fills it."""
         self.reserve(1)
         row, self.used = self.used, self.used + 1
         self.provenance.append((song, int(r0), int(bars)))
+        self._groups.append(self._group_of.setdefault(song, len(self._group_of)))
         self.by_song.setdefault(song, []).append(row)
         return row
 
@@ -777,6 +786,100 @@ class StyleBank:
         if not rows:
             raise KeyError(f'StyleBank: no rows of song {song!r}')
         return [(r, np.float32(1.) / np.float32(len(rows))) for r in rows]
+
+    def group_of(self, song):
+        """The group of the song's rows — its ordinal among the bank's songs — or -1 for a song the bank does not hold."""
+        return self._group_of.get(song, -1)
+
+    def exclusions(self, nearest, songs):
+        """Per clip of `songs` the group a search for `nearest` (a Nearest) leaves out: the song's own, or -1 — nothing — without
+        exclude_own or for a song the bank does not hold.  ValueError when the bank holds fewer than nearest.k rows outside the
+        largest excluded song: some clip would be left with a -1 among its rows."""
+        groups = [self.group_of(song) if nearest.exclude_own else -1 for song in songs]
+        most = max((len(self.by_song[song]) for song, g in zip(songs, groups) if g >= 0), default=0)
+        if self.used - most < nearest.k:
+            raise ValueError(f'{nearest!r} on a StyleBank of {self.used} rows, {most} of them of one excluded song: fewer than '
+                             f'{nearest.k} rows are left to pick from')
+        return groups
+
+    def device_groups(self):
+        """The device copy of the rows' groups, brought up to date (a copy of the rows taken since the last call: never during
+        a capture)."""
+        if self._groups_on_device < self.used:
+            _not_while_capturing(self.device)
+            new = torch.tensor(self._groups[self._groups_on_device:self.used], dtype=torch.int32)
+            self.groups[self._groups_on_device:self.used].copy_(new)
+            self._groups_on_device = self.used
+        return self.groups
+
+    def search(self, queries, k, exclude=None, farthest=False, native=None):
+        """The `k` rows of the bank nearest to (or, with `farthest`, farthest from) each of Q query styles by cosine, ranked on
+        the device by mst_style_search: -> (rows (Q, k) int32, scores (Q, k) float32) as numpy after one download; positions
+        past the last rankable row hold -1 / NaN.  `queries` is a float32 tensor (Q, style_size) on the bank's device, or Q
+        entry lists (`row`, `song`, `blend`), which mst_style_mix turns into a query buffer first.  `exclude`: Q song names or
+        Nones; the rows of query q's song are left out for it (a song the bank does not hold leaves out nothing).  Only the
+        first len(bank) rows are searched.  `native`: the library to call (default: the product library)."""
+        from style import _native
+        native = native or _native.get()
+        k = int(k)
+        if not 1 <= k <= _native.SEARCH_MAX_K:
+            raise ValueError(f'StyleBank.search: k = {k}, not in [1, {_native.SEARCH_MAX_K}]')
+        stream = _native.current_stream(self.device)
+        if torch.is_tensor(queries):
+            if queries.dim() != 2 or queries.shape[1] != self.style_size or queries.dtype != torch.float32 or queries.device != self.rows.device:
+                raise ValueError(f'StyleBank.search: queries of {tuple(queries.shape)} {queries.dtype} on {queries.device}, not '
+                                 f'(Q, {self.style_size}) float32 on {self.rows.device}')
+            queries = queries.contiguous()
+        else:
+            offsets, idx, w = StyleBank.mix(queries)
+            if len(idx) == 0:
+                raise ValueError('StyleBank.search: no query')
+            entries = [torch.from_numpy(a).to(self.device) for a in (offsets, idx, w)]
+            queries = torch.empty(len(offsets) - 1, self.style_size, dtype=torch.float32, device=self.device)
+            native.style_mix(self.rows, self.capacity, self.style_size, *entries, len(idx), queries, self.style_size, len(queries),
+                             self.style_size, stream)
+        Q = len(queries)
+        if not 1 <= Q <= 4096:
+            raise ValueError(f'StyleBank.search: {Q} queries, not in [1, 4096]')
+        if exclude is not None and len(exclude) != Q:
+            raise ValueError(f'StyleBank.search: {len(exclude)} exclusions for {Q} queries')
+        groups = self.device_groups()
+        small = torch.tensor([self.used] + [-1 if e is None else self.group_of(e) for e in (exclude or [None] * Q)], dtype=torch.int32)
+        small = small.to(self.device)
+        key = (self.capacity, Q, k)
+        if key not in self._search:                             # (one scratch per shape in use; a grown bank drops the old ones)
+            self._search = {s: t for s, t in self._search.items() if s[0] == self.capacity}
+            self._search[key] = torch.empty(native.style_search_scratch_bytes(self.capacity, Q, k) // 8, dtype=torch.int64, device=self.device)
+        rows = torch.empty(Q, k, dtype=torch.int32, device=self.device)
+        scores = torch.empty(Q, k, dtype=torch.float32, device=self.device)
+        native.style_search(self.rows, self.capacity, self.style_size, small[:1], groups, queries, Q, self.style_size, small[1:], self.style_size,
+                            k, -1 if farthest else 1, rows, scores, self._search[key], stream)
+        return rows.cpu().numpy(), scores.cpu().numpy()
+
+    def song_means(self, native=None):
+        """A new StyleBank on the same device with one row per song, in `by_song`'s order: the song's mean style, mixed on the
+        device by mst_style_mix from `song(s)`; its provenance is (song, 0, the summed bars of the song's rows)."""
+        from style import _native
+        native = native or _native.get()
+        means = StyleBank(self.style_size, self.device, capacity=max(len(self.by_song), 1))
+        if not self.by_song:
+            return means
+        offsets, idx, w = StyleBank.mix([self.song(song) for song in self.by_song])
+        for song, rows in self.by_song.items():
+            means.take(song, 0, sum(self.provenance[r][2] for r in rows))
+        entries = [torch.from_numpy(a).to(self.device) for a in (offsets, idx, w)]
+        native.style_mix(self.rows, self.capacity, self.style_size, *entries, len(idx), means.rows, self.style_size, len(self.by_song),
+                         self.style_size, _native.current_stream(self.device))
+        return means
+
+    def neighbours(self, song, k, farthest=False, native=None):
+        """[(other song, cosine), ...]: the `k` songs whose mean style is nearest to (farthest from) the mean style of `song`,
+        the song itself left out; fewer than k when the bank holds fewer other songs."""
+        if song not in self.by_song:
+            raise KeyError(f'StyleBank: no rows of song {song!r}')
+        means = self.song_means(native)
+        rows, scores = means.search([means.song(song)], k, exclude=[song], farthest=farthest, native=native)
+        return [(means.provenance[r][0], float(s)) for r, s in zip(rows[0].tolist(), scores[0].tolist()) if r >= 0]
 
     def blend(self, parts):
         """[(what, weight), ...] -> the concatenated entries, each weight scaled (a float32 product).  `what` is a list of entries
@@ -820,6 +923,25 @@ class StyleBank:
                 bank.take(int(song) if is_int else song, r0, bars)
             bank.rows[:len(rows)].copy_(torch.from_numpy(rows))
         return bank
+
+
+class Nearest:
+    """A `mix` for StyleTransferModel.transfer_styles that names no rows: every clip is rendered with the uniform blend (weights
+    float32(1) / float32(k)) of the `k` rows of the bank whose cosine to the clip's own style is largest — or, with `farthest`,
+    smallest — found on the device by mst_style_search.  `exclude_own`: rows of the clip's own song do not count."""
+
+    def __init__(self, k=1, exclude_own=True, farthest=False):
+        from style._native import SEARCH_MAX_K
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= SEARCH_MAX_K:
+            raise ValueError(f'Nearest: k = {k!r}, not an int in [1, {SEARCH_MAX_K}]')
+        self.k, self.exclude_own, self.farthest = int(k), bool(exclude_own), bool(farthest)
+
+    @property
+    def order(self):
+        return -1 if self.farthest else 1
+
+    def __repr__(self):
+        return f'Nearest(k={self.k}, exclude_own={self.exclude_own}, farthest={self.farthest})'
 
 
 def prepare_input_sparse(input, max_n_bars=None, pin=None):

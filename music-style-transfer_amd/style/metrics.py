@@ -168,13 +168,16 @@ class TransferResult:
     percussion) are on the device, else None.  transfer_styles adds `instr_features` (K, C, 51: the instrument rows the clips
     were rendered with) and, where the device decided them, `decisions` (K, C + 2 int32, mst_info_decide's records: the C picked
     logit indices, percussion's position in the ranking, the mode index), both on the device; transfer_windows leaves them None.
-    Every tensor is the result's own: a later call does not change it."""
+    With mix=style.data.Nearest(k) transfer_styles also leaves `neighbours` (K, k int32: the bank rows mst_style_search picked
+    for each clip, nearest or farthest first) and `neighbour_scores` (K, k float32: their cosines), on the device; both are None
+    for every other mix.  Every tensor is the result's own: a later call does not change it."""
 
     def __init__(self, instruments_pred, mode_pred, bpm_pred, pitched, unpitched, style_sums=None, retention=None, decisions=None,
-                 instr_features=None):
+                 instr_features=None, neighbours=None, neighbour_scores=None):
         self.instruments_pred, self.mode_pred, self.bpm_pred = instruments_pred, mode_pred, bpm_pred
         self.pitched, self.unpitched, self.style_sums, self.retention = pitched, unpitched, style_sums, retention
         self.decisions, self.instr_features = decisions, instr_features
+        self.neighbours, self.neighbour_scores = neighbours, neighbour_scores
 
     @property
     def cosines(self):

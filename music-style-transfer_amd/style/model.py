@@ -990,14 +990,29 @@ class StyleTransferModel(nn.Module):
         windows and other mixes.  A clip whose entries are empty or name a row outside the bank gets NaNs for a style, which
         show in its predictions; rows at or beyond len(bank) but inside its capacity are not checked.
 
+        `mix` may also be a style.data.Nearest(k, exclude_own, farthest): no rows are named, and behind the extract stage
+        mst_style_search ranks the clips' own styles (the K `style` slots, the plan's clip stride apart) against the first
+        len(bank) rows and writes the k nearest (farthest) rows of every clip into the CSR's idx on the device; offsets are
+        arange(K + 1) k and every weight float32(1) / float32(k), so the chain goes on unchanged with the uniform blend of the
+        neighbours, in the same graph and with no host round trip.  With `exclude_own` the rows of the clip's own song (its group
+        in the bank) do not count.  ValueError when the bank holds fewer than k rows outside the largest excluded song, so
+        that no clip is left with a -1 among its rows.  The result then carries `neighbours` and `neighbour_scores` (K, k).
+
         Returns a style.metrics.TransferResult with `instr_features` (K, C, 51) and, where the device decided, `decisions`
         (K, C + 2 int32).  What transfer_windows says about streams, lanes and the training state holds here: the states are
         this method's own."""
-        from style.data import StyleBank, group_of_instrument
+        from style.data import Nearest, StyleBank, group_of_instrument
         K, C = batch.K, batch.C
         dev = self._anchor().device
         if bank.rows.device != dev:
             raise _native.MstError(f'the StyleBank lives on {bank.rows.device}, the model on {dev}')
+        nearest = mix if isinstance(mix, Nearest) else None
+        exclude = np.full(K, -1, dtype=np.int32)
+        if nearest is not None:
+            exclude[:] = bank.exclusions(nearest, batch.songs.tolist())
+            # the search fills idx on the device; offsets and weights are the uniform blend of k rows per clip
+            mix = (np.arange(K + 1) * nearest.k, np.full(K * nearest.k, -1), np.full(K * nearest.k, np.float32(1.) / np.float32(nearest.k)))
+            groups = bank.device_groups()                       # (brought up to date here: never during a capture)
         offsets, idx, w = mix if isinstance(mix, tuple) and len(mix) == 3 and not isinstance(mix[0], list) else StyleBank.mix(mix)
         offsets, idx = np.asarray(offsets, dtype=np.int32).reshape(-1), np.asarray(idx, dtype=np.int32).reshape(-1)
         w = np.ascontiguousarray(np.asarray(w, dtype=np.float32).reshape(-1))
@@ -1018,7 +1033,8 @@ class StyleTransferModel(nn.Module):
         else:
             raise ValueError(f"transfer_styles: instruments is 'each', 'pooled' or a tensor, not {instruments!r}")
         live = K if live is None else int(live)
-        at_off, at_live, at_idx, at_w = K, 2 * K + 1, 2 * K + 2, 2 * K + 2 + entry_cap      # the tail: targets, offsets, live, idx, w
+        at_off, at_live, at_idx, at_w = K, 2 * K + 1, 2 * K + 2, 2 * K + 2 + entry_cap      # the tail: targets, offsets, live, idx, w,
+        at_ex, at_used = at_w + entry_cap, at_w + entry_cap + K                             # the clips' excluded groups, len(bank)
 
         def fill(tail, own):
             tail[:K] = np.arange(K, 2 * K)                      # mst_style_sums: clip k's target is row K + k of the side buffer
@@ -1027,7 +1043,9 @@ class StyleTransferModel(nn.Module):
             tail[at_idx:at_idx + n_entries] = idx
             tail[at_idx + n_entries:at_w] = -1
             tail[at_w:at_w + n_entries] = w.view(np.int32)
-            tail[at_w + n_entries:] = 0
+            tail[at_w + n_entries:at_ex] = 0
+            tail[at_ex:at_used] = exclude
+            tail[at_used] = len(bank)
 
         def render(c):
             plan, ws, native, st = c.plan, c.ws, c.native, c.st
@@ -1036,6 +1054,10 @@ class StyleTransferModel(nn.Module):
             if score:                                           # the own styles: rows [0, K) of the side buffer
                 native.clip_gather(c.style_slots, K, plan.clip_stride, side, c.style_size, None, K, c.style_size, c.stream())
             # (the bank's capacity, not its fill: a capture stays right while rows are added until the bank moves)
+            if nearest is not None:                             # the clips' own styles are the queries; the rows land in idx
+                native.style_search(rows, rows.shape[0], c.style_size, c.tail[at_used:], groups, c.style_slots, K, plan.clip_stride,
+                                    c.tail[at_ex:], c.style_size, nearest.k, nearest.order, c.tail[at_idx:], st['neighbour_scores'],
+                                    st['search_scratch'][(rows.shape[0], nearest.k)], c.stream())
             native.style_mix(rows, rows.shape[0], c.style_size, c.tail[at_off:], c.tail[at_idx:], c.tail[at_w:].view(torch.float32),
                              entry_cap, c.style_slots, plan.clip_stride, K, c.style_size, c.stream())
             if score:                                           # the mixed targets: rows [K, 2 K)
@@ -1064,13 +1086,26 @@ class StyleTransferModel(nn.Module):
                 if given[0].numel() != plan.slot('instr')[2]:
                     raise ValueError(f'transfer_styles: instrument rows of {given[0].numel()} floats, the plan reads {plan.slot("instr")[2]}')
                 st['given'][:given.shape[0]].copy_(given.reshape(given.shape[0], -1))
+            if nearest is not None:
+                if 'neighbour_scores' not in st:
+                    st['neighbour_scores'] = torch.zeros(K * _native.SEARCH_MAX_K, dtype=torch.float32, device=dev)
+                    st['search_scratch'] = {}
+                shape = (bank.rows.shape[0], nearest.k)
+                if shape not in st['search_scratch']:
+                    st['search_scratch'][shape] = torch.empty(_native.get().style_search_scratch_bytes(shape[0], K, nearest.k) // 8,
+                                                              dtype=torch.int64, device=dev)
 
         def finish(c, result, rows_of):
             result.instr_features = rows_of('instr').view(K, C, -1)
             result.decisions = c.st['decisions'].clone() if given is None else None
+            if nearest is not None:
+                result.neighbours = c.tail[at_idx:at_idx + n_entries].view(K, nearest.k).clone()
+                result.neighbour_scores = c.st['neighbour_scores'][:n_entries].view(K, nearest.k).clone()
 
         key_extra = (kind, entry_cap, bank.rows.data_ptr(), bank.rows.shape[0], None if given is None else given.shape[0])
-        return self._transfer_pass('transfer_styles', state_of, store, batch, at_w + entry_cap, 2 * K, fill, render, key_extra, score,
+        if nearest is not None:
+            key_extra += (('nearest', nearest.k, nearest.order, nearest.exclude_own), groups.data_ptr())
+        return self._transfer_pass('transfer_styles', state_of, store, batch, at_used + 1, 2 * K, fill, render, key_extra, score,
                                    capacity, finish=finish, prepare=prepare)
 
     def eval_accumulator(self):

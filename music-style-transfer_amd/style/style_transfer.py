@@ -54,7 +54,7 @@ def transfer_style(model, composition_path, style_paths, output_path, sparse_out
 
 
 def transfer_songs(model, composition_path, style_paths, output_path, bars=16, K=8, score=False, song_styles=False, blends=(),
-                   instruments='donor'):
+                   instruments='donor', library=None, nearest=0):
     """`transfer_style` on resident songs, K windows per pass (StyleTransferModel.transfer_windows): the composition and the
     style songs are loaded as `transfer_style` loads them, kept in a SongStore on the model's device, and for every style song
     the composition's consecutive `bars`-bar windows (the last one zero-extended) are rendered with the style and the
@@ -82,13 +82,23 @@ def transfer_songs(model, composition_path, style_paths, output_path, bars=16, K
     instruments='predicted': the clips play what the model predicts, not the donor's programs — apply_style's rule, decided on
     the device (mst_info_decide) once per file, on the predictions summed over the live windows of the file's first batch; the
     later batches reuse that batch's instrument rows, and the programs written are the decided ones.  The donor's instrument
-    rows are then not needed, so a style song of another bucket than the composition's is accepted."""
-    from style.data import SongStore, WindowBatch, prepare_input_sparse
+    rows are then not needed, so a style song of another bucket than the composition's is accepted.
+
+    library=a style.data.StyleBank on the model's device or the path of one saved with StyleBank.save, nearest=k > 0: besides
+    the files above, '{composition} (library style).mid', every composition window rendered with the uniform blend of the k
+    rows of the library nearest to the window's own style by cosine (StyleTransferModel.transfer_styles with
+    style.data.Nearest(k, exclude_own=False): searched, mixed and rendered on the device).  A library has no donor instrument
+    rows, so the instruments are the 'predicted' ones, and scale and style name are the composition's.  The call then returns
+    the result dict also without `score`, with the picked rows' provenance under the key 'library' — per composition window the
+    k (song, first bar, bars) — and with `score` the file's scores under 'library style'."""
+    from style.data import Nearest, SongStore, StyleBank, WindowBatch, prepare_input_sparse
     from style.metrics import NoteMetrics, style_cosines
     from style.sparse import crop_bars, stitch_records
-    bars, K = int(bars), int(K)
+    bars, K, nearest = int(bars), int(K), int(nearest)
     if bars < 1 or K < 2:
         raise ValueError('transfer_songs: bars >= 1, and K >= 2 (a batch holds the donor window and at least one other)')
+    if nearest < 0 or (nearest > 0 and library is None):
+        raise ValueError(f'transfer_songs: nearest = {nearest} needs nearest >= 0 and, above 0, a library')
     play = instruments
     if play not in ('donor', 'predicted'):
         raise ValueError(f"transfer_songs: instruments is 'donor' or 'predicted', not {play!r}")
@@ -148,6 +158,26 @@ def transfer_songs(model, composition_path, style_paths, output_path, bars=16, K
             scores[style_name] = _write_transfer(got, composition_info, song_info, donor_programs, C, R, U, bars, score,
                                                  os.path.join(output_path, f'{composition_name} ({style_name} style).mid'))
         jobs = jobs[:1]                                         # the reconstruction is transfer_windows', as ever
+    if nearest > 0:
+        if not isinstance(library, StyleBank):
+            library = StyleBank.load(library, store.device)
+        got, rows, picks = [], None, []
+        for at in range(0, len(starts), K):
+            part = starts[at:at + K]
+            live = len(part)
+            batch = WindowBatch(C, bars, T, U, [0] * K, part + [part[-1]] * (K - live))
+            res = model.transfer_styles(store, batch, library, Nearest(nearest, exclude_own=False), instruments='pooled' if rows is None else rows,
+                                        score=score, live=live)
+            if rows is None:                                    # the file's one decision, as for instruments='predicted'
+                rows, picked = res.instr_features[:1].clone(), res.decisions[0, :C].cpu().tolist()
+                programs = [_instrument_categories[i] for i in picked]
+            picks += [[library.provenance[r] for r in window] for window in res.neighbours[:live].cpu().tolist()]
+            got.append((res, live))
+        scored = _write_transfer(got, composition_info, composition_info, programs, C, R, U, bars, score,
+                                 os.path.join(output_path, f'{composition_name} (library style).mid'))
+        scores['library'] = picks
+        if score:
+            scores['library style'] = scored
     for song, song_info, instruments, style_name in jobs:
         got = []
         for at in range(0, len(starts), K - 1):
@@ -172,7 +202,7 @@ def transfer_songs(model, composition_path, style_paths, output_path, bars=16, K
             retention = torch.cat([res.retention[:live] for res, live in got]).cpu()
             scores[style_name] = dict(cosines=np.concatenate([style_cosines(res.style_sums)[:live] for res, live in got]).mean(0),
                                       pitched=NoteMetrics(retention[:, :-1]).sum(), unpitched=NoteMetrics(retention[:, -1]).sum())
-    return scores if score else None
+    return scores if score or nearest > 0 else None
 
 
 def _write_transfer(got, composition_info, style_info, programs, C, R, U, bars, score, path):

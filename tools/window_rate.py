@@ -28,9 +28,14 @@ and their spread).
                was, on the same store, so that one captured graph serves both legs); reported are both rates, their ratio and the host time of `admit` on the loop thread; and, under
                device events, one refresh of four songs: the mst_store_admit launch against the 5 x 4 separate copies `add`
                makes for the same songs and against a device-to-device copy of the same bytes.
+  --search     times style search alone (no songs, no model): mst_style_search of Q = 64 queries against N = 4 096 and 65 536
+               rows of D = 256 floats, k = 8, under device events — the call, and its two launches apart (kernel durations
+               from torch.profiler; null where the profiler reports none) — beside a device-to-device copy of the bank's bytes
+               (the floor of a kernel that reads the bank once) and torch's own normalize -> matmul -> topk on the same
+               tensors; and whether scores and rows came back bit-equal to the host's float32 fmaf chain.
 One JSON line per measurement; --out writes them all to a file.
 Usage on the GPU box: python tools/window_rate.py [--songs 16] [--iters 150] [--runs 5] [--one-clip] [--kernels] [--eval
-                      [--eval-stride S]] [--transfer] [--styles] [--rotate] [--out FILE]"""
+                      [--eval-stride S]] [--transfer] [--styles] [--rotate] [--search] [--out FILE]"""
 import argparse
 import json
 import os
@@ -569,6 +574,83 @@ def rotate(model, opt, songs, clips, iters, runs):
     return results
 
 
+def host_chain(queries, bank):
+    """mst_amd.h's score of every (query, row) pair on the host: the float32 fmaf chains (the product of two floats is exact in
+    float64, so float32(float64 product + float64 acc) is the fma), np.sqrt and / in float32."""
+    def dots(a, b):
+        acc = np.zeros((len(a), len(b)), dtype=np.float32)
+        for i in range(a.shape[1]):
+            acc = (a[:, i, None].astype(np.float64) * b[None, :, i].astype(np.float64) + acc.astype(np.float64)).astype(np.float32)
+        return acc
+
+    def squares(a):
+        acc = np.zeros(len(a), dtype=np.float32)
+        for i in range(a.shape[1]):
+            acc = (a[:, i].astype(np.float64) ** 2 + acc.astype(np.float64)).astype(np.float32)
+        return acc
+    return dots(queries, bank) / (np.sqrt(squares(queries))[:, None] * np.sqrt(squares(bank))[None, :])
+
+
+def search_kernels(N, D=256, Q=64, k=8, reps=50):
+    """Microseconds, under device events, of mst_style_search (Q queries, N rows of D floats, the k nearest), of a copy of the
+    bank's bytes and of torch's normalize -> matmul -> topk, alternated; the call's two launches apart from torch.profiler; and
+    the comparison of scores and rows with the host chain."""
+    from style import _native
+    native, dev = _native.get(), torch.device('cuda:0')
+    g = torch.Generator().manual_seed(N)
+    bank = torch.randn(N, D, generator=g).to(dev)
+    queries = torch.randn(Q, D, generator=g).to(dev)
+    other = torch.empty_like(bank)
+    rows = torch.empty(Q, k, dtype=torch.int32, device=dev)
+    scores = torch.empty(Q, k, device=dev)
+    scratch = torch.empty(native.style_search_scratch_bytes(N, Q, k) // 8, dtype=torch.int64, device=dev)
+    stream = _native.current_stream(dev)
+    search = lambda: native.style_search(bank, N, D, None, None, queries, Q, D, None, D, k, 1, rows, scores, scratch, stream)
+
+    def by_torch():
+        cos = torch.nn.functional.normalize(queries, dim=1) @ torch.nn.functional.normalize(bank, dim=1).T
+        return torch.topk(cos, k, dim=1)
+    calls = (('mst_style_search', search), ('device-to-device copy of the bank', lambda: other.copy_(bank)),
+             ('torch normalize -> matmul -> topk', by_torch))
+    res = []
+    for name, fn in calls + calls:                         # alternated
+        fn()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            times.append(a.elapsed_time(b) * 1e3)
+        res.append(dict(what=name, N=N, D=D, Q=Q, k=k, bank_bytes=4 * N * D, unit='us', **spread(times)))
+    launches = {}
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            for _ in range(reps):
+                search()
+            torch.cuda.synchronize()
+        for e in prof.events():
+            if 'style_search' in e.name:
+                launches.setdefault('merge' if 'merge' in e.name else 'scores and slab selection', []).append(float(e.device_time))
+    except Exception as err:                               # the split is a report, not a dependency
+        launches = {'error': [repr(err)]}
+    res.append(dict(what='mst_style_search by launch (torch.profiler kernel durations)', N=N, D=D, Q=Q, k=k, unit='us',
+                    **{name: spread(t) if t and not isinstance(t[0], str) else t for name, t in launches.items()}))
+    search()
+    torch.cuda.synchronize()
+    got_rows, got_scores = rows.cpu().numpy(), scores.cpu().numpy()
+    want = host_chain(queries.cpu().numpy(), bank.cpu().numpy())
+    order = np.lexsort((np.broadcast_to(np.arange(N), want.shape), -want), axis=1)[:, :k]          # descending, ties by row
+    torch_rows = by_torch()[1].cpu().numpy()
+    res.append(dict(what='mst_style_search against the host chain', N=N, D=D, Q=Q, k=k,
+                    scores_bit_equal=bool(np.array_equal(got_scores.view(np.uint32), np.take_along_axis(want, got_rows.astype(np.int64), 1).view(np.uint32))),
+                    rows_equal=bool(np.array_equal(got_rows, order)), rows_equal_to_torch_topk=bool(np.array_equal(got_rows, torch_rows))))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--songs', type=int, default=16)
@@ -582,10 +664,20 @@ def main():
     ap.add_argument('--transfer', action='store_true')
     ap.add_argument('--styles', action='store_true')
     ap.add_argument('--rotate', action='store_true')
+    ap.add_argument('--search', action='store_true')
     ap.add_argument('--out')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('window_rate.py measures on the GPU; there is none here')
+    if args.search:
+        results = [r for N in (4096, 65536) for r in search_kernels(N)]
+        for r in results:
+            print(json.dumps(r))
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, 'w') as f:
+                f.writelines(json.dumps(r) + '\n' for r in results)
+        return
     from style.optim import FusedAdam
     from style.train import build_model, fill_store
     songs = synth_songs(args.songs)
